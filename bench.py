@@ -13,10 +13,17 @@ Philox (seed 42), tactics aggressive, side blue, trained red. Total work is
 fixed as N grows (strong scaling); `--envs E` instead fixes E envs per GPU
 (weak scaling). A "step" = one Game.step over every env of the GPU; inputs
 (actions for all timed steps) are resident in HBM before the timed region.
-At N=1 the line also carries `secondary` measurements: config 3's per-GPU
-shard (8 192 envs) and config 2 (4 096), melee spawns, the unpruned LOS
-march / A* mode, config 4 and config 5, each with its kernel time and the
-fraction of the HBM roofline its algorithmic bytes reach.
+
+A plain run does only what the headline figure needs: set up, warm up, time
+the K steps, print the line. `--dump-outputs DIR` also writes what the last
+timed step returned (`DIR/<name>.npy`; the inputs depend on the arguments
+alone, so two builds can be compared output for output). Everything else sits
+behind `--full`: the CPU baseline, the device work counters of the timed window
+(`los_work`, an untimed replay), and at N=1 the `secondary` measurements:
+config 3's per-GPU shard (8 192 envs) and config 2 (4 096), melee spawns, the
+unpruned LOS march / A* mode, config 4 and config 5, each with its kernel time
+and the fraction of the HBM roofline its algorithmic bytes reach (at N>1,
+config 5 split over the ranks).
 """
 import argparse
 import ctypes
@@ -84,14 +91,22 @@ def parse():
                         "(diagnostics, e.g. with LNW_PROF=1)")
     p.add_argument("--los-mode", type=int, default=0, help="0 LOS table, 1 ray march")
     p.add_argument("--move-mode", type=int, default=0, help="0 move table, 1 direct A*")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline does not need: the CPU baseline, the "
+                        "work counters of the timed window (los_work) and the secondary lines")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the arrays the last timed step returned to DIR/<name>.npy (a fixed "
+                        "seeded sample of the envs where they exceed DUMP_BYTES)")
+    p.add_argument("--no-cpu-baseline", action="store_true",
+                   help="with --full: skip the CPU baseline")
     p.add_argument("--cpu-seconds", type=float, default=12.0)
     p.add_argument("--cpu-threads", type=int, default=min(16, os.cpu_count() or 1),
                    help="threads for the CPU baseline (the GPU box's share is 16 cores)")
     p.add_argument("--episode-steps", type=int, default=40,
                    help="episode horizon (config.json: 40); diagnostics only")
     p.add_argument("--no-secondary", action="store_true",
-                   help="skip the secondary lines (configs 2, 3-shard, 4, 5, melee, march)")
+                   help="with --full: skip the secondary lines (configs 2, 3-shard, 4, 5, melee, "
+                        "march)")
     p.add_argument("--secondary-steps", type=int, default=100)
     p.add_argument("--dry-run", action="store_true",
                    help="launcher plumbing only (runs without a GPU): the ranks start, join the "
@@ -155,52 +170,92 @@ def make_game(E, env_base, spawns, los_mode, move_mode, cfg=None):
     return g
 
 
+ACTION_BYTES = 16 << 30  # action sets resident in HBM at a time (a window of steps)
+DUMP_BYTES = 48 << 20    # --dump-outputs: most it writes (float32 / float64 arrays)
+OUTPUT_NAMES = ("obs_blue", "obs_red", "rew_blue", "rew_red", "done", "cog")
+
+
+def sample_outputs(out, E):
+    """What the last step returned (BatchedGame.step's tensors), on the host in
+    float32 (float64 where the step wrote float64): every env where that stays
+    within DUMP_BYTES, else the envs of a fixed seeded sample, in env order."""
+    per_env = sum(out[k][0].numel() * (8 if out[k].dtype == torch.float64 else 4)
+                  for k in OUTPUT_NAMES)
+    n = min(E, max(1, DUMP_BYTES // per_env))
+    idx = None
+    if n < E:
+        pick = np.sort(np.random.default_rng(0).choice(E, n, replace=False))
+        idx = torch.from_numpy(pick).to(out["done"].device)
+    res = {}
+    for k in OUTPUT_NAMES:
+        t = out[k] if idx is None else out[k][idx]
+        res[k] = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+    return res
+
+
 def run_workload(E, env_base, spawns, los_mode, move_mode, steps, warmup, cfg=None, digest=False,
-                 count_work=True):
+                 count_work=True, outputs=False):
     """Create the envs [env_base, env_base + E) of one rank, fill the actions of
     every step (Philox keyed by global env id and step, so a global env's
     inputs do not depend on the sharding), run `warmup` untimed steps, then
     time `steps` launches between barriers. Returns a dict: wall seconds, mean
     kernel ms from HIP events on the launch stream, envs with error bits,
-    episodes completed, with `count_work` the device work counters (rays /
+    episodes completed, with `outputs` the arrays the last timed step returned
+    (sample_outputs), with `count_work` the device work counters (rays /
     cells marched, A* searches, pooled bearings) per env-step over exactly the
     timed window (a second, untimed pass that replays the same warmup and timed
     steps from the same initial state with the counters bound: the step is
     deterministic, so it walks the same trajectory), and with `digest` the
     per-env final state."""
-    from lnw import _abi
+    from lnw import _abi, dist
     L = _abi.load()
     g = make_game(E, env_base, spawns, los_mode, move_mode, cfg)
     A = g.A
-    # inputs resident before the timed region: actions for every step; the
+    # inputs resident before the timed region: the actions of every step of a
+    # window (all the steps, unless they exceed ACTION_BYTES: then window after
+    # window is filled untimed and timed on its own, and the times add up); the
     # value of (global env, agent, component) at step s sits at Philox counter
     # offset s * 2^40 + (env * A + agent) * 4 + component
-    acts = torch.empty((warmup + steps, E, A, 4), dtype=torch.float32, device="cuda")
     per = E * A * 4
+    window = max(1, min(max(warmup, steps), ACTION_BYTES // (per * 4)))
+    acts = torch.empty((window, E, A, 4), dtype=torch.float32, device="cuda")
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    for s in range(warmup + steps):
-        off = (s << 40) + env_base * A * 4
-        _abi.check(L.lnw_fill_uniform_f32(ctypes.c_void_p(acts[s].data_ptr()), per, 42, off, stream))
-    torch.cuda.synchronize()
-    for s in range(warmup):
-        g.step(acts[s])
-    torch.cuda.synchronize()
     # HIP events on the stream the step kernel is launched on (torch's current
-    # stream), bracketing the K back-to-back launches of the timed region
+    # stream), bracketing the back-to-back launches of a timed window
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    from lnw import dist
-    dist.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    ev0.record()
-    for s in range(steps):
-        g.step(acts[warmup + s])
-    ev1.record()
-    torch.cuda.synchronize()
-    dist.barrier()
-    t1 = time.perf_counter()
-    elapsed = t1 - t0
-    kms = ev0.elapsed_time(ev1) / steps
+
+    def run(game, s0, n, timed=False):
+        """Steps s0 .. s0 + n - 1; returns (wall seconds, kernel ms) if timed."""
+        wall = kms = 0.0
+        for w0 in range(s0, s0 + n, window):
+            m = min(window, s0 + n - w0)
+            for i in range(m):
+                off = ((w0 + i) << 40) + env_base * A * 4
+                _abi.check(L.lnw_fill_uniform_f32(ctypes.c_void_p(acts[i].data_ptr()), per, 42, off,
+                                                  stream))
+            torch.cuda.synchronize()
+            if timed:
+                dist.barrier()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                ev0.record()
+            for i in range(m):
+                game.step(acts[i])
+            if timed:
+                ev1.record()
+                torch.cuda.synchronize()
+                dist.barrier()
+                wall += time.perf_counter() - t0
+                kms += ev0.elapsed_time(ev1)
+        torch.cuda.synchronize()
+        return wall, kms
+
+    run(g, 0, warmup)
+    elapsed, kms = run(g, warmup, steps, timed=True)
+    kms /= steps
+    # step() returns the game's own output tensors: after the last timed step
+    # they hold what that step computed
+    last = sample_outputs({k: getattr(g, k) for k in OUTPUT_NAMES}, E) if outputs else None
     st = g.env_state()
     err = int((st["err"] != 0).sum())
     episodes = int(st["episode"].sum())
@@ -212,12 +267,9 @@ def run_workload(E, env_base, spawns, los_mode, move_mode, steps, warmup, cfg=No
         final = {k: st[k].copy() for k in ("rng", "episode", "steps_done")}
         g.close()
         g = make_game(E, env_base, spawns, los_mode, move_mode, cfg)
-        for s in range(warmup):
-            g.step(acts[s])
+        run(g, 0, warmup)
         g.count_work(True)
-        for s in range(steps):
-            g.step(acts[warmup + s])
-        torch.cuda.synchronize()
+        run(g, warmup, steps)
         work = {k: v / (E * steps) for k, v in g.work_counts().items()}
         g.count_work(False)
         st2 = g.env_state()
@@ -235,7 +287,15 @@ def run_workload(E, env_base, spawns, los_mode, move_mode, steps, warmup, cfg=No
     g.close()
     del acts
     return dict(elapsed=elapsed, kernel_ms=kms, err=err, episodes=episodes, digest=dig,
-                work_per_env_step=work)
+                work_per_env_step=work, outputs=last)
+
+
+def write_outputs(path, outputs, rank, world):
+    """--dump-outputs: DIR/<name>.npy (DIR/<name>_rank<r>.npy at N > 1, each
+    rank its own envs)."""
+    os.makedirs(path, exist_ok=True)
+    for k, v in outputs.items():
+        np.save(os.path.join(path, k + (f"_rank{rank}" if world > 1 else "") + ".npy"), v)
 
 
 def measured_traffic(args, E):
@@ -538,7 +598,9 @@ def main():
         E, env_base = hi - lo, lo
         scaling = "strong"
     res = run_workload(E, env_base, args.spawns, args.los_mode, args.move_mode, args.steps,
-                       args.warmup, cfg)
+                       args.warmup, cfg, count_work=args.full, outputs=args.dump_outputs is not None)
+    if args.dump_outputs is not None:
+        write_outputs(args.dump_outputs, res["outputs"], rank, world)
     elapsed, kms_mean, err, episodes = res["elapsed"], res["kernel_ms"], res["err"], res["episodes"]
     elapsed, kms_mean = dist.reduce_max([elapsed, kms_mean])
     err, episodes = (int(v) for v in dist.reduce_sum([err, episodes]))
@@ -548,13 +610,13 @@ def main():
     achieved = B * E / (kms_mean * 1e-3) / 1e9
     traffic = measured_traffic(args, E)
     secondary = {}
-    if world == 1 and not args.no_secondary and cfg is None:
+    if args.full and world == 1 and not args.no_secondary and cfg is None:
         secondary = secondary_lines(args)
-    elif world > 1 and not args.no_secondary and cfg is None:
+    elif args.full and world > 1 and not args.no_secondary and cfg is None:
         # config 5 is quoted on 8 GPUs: its 32 768 envs split over the ranks
         secondary = {"config5_mappo_rollout": mappo_rollout()}
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.cpu_seconds, args.cpu_threads)
     if rank == 0:
         line = {
@@ -565,6 +627,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": elapsed / args.steps * 1e3,
             "higher_is_better": True,
             "scaling": scaling,
@@ -600,7 +663,9 @@ def main():
             "err_envs": err,
             "episodes_completed": episodes,
         }
-        if cfg is None and args.spawns == "reference" and args.los_mode == 0:
+        if args.dump_outputs is not None:
+            line["outputs"] = {k: list(v.shape) for k, v in res["outputs"].items()}
+        if args.full and cfg is None and args.spawns == "reference" and args.los_mode == 0:
             # SURVEY §8(d) secondary work metric: the reference marches a Bresenham
             # ray for every own x opponent pair of every get_obs, 10 996 cells per
             # 4v4 env-step at these spawns (measured there)

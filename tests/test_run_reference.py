@@ -8,11 +8,8 @@ import os
 import subprocess
 import sys
 
-import pytest
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "littoral-naval-warfare-marl_amd")
-REF = "/root/reference"
 
 DECOY = "raise ImportError('decoy game.py next to the script was imported')\n"
 
@@ -87,18 +84,29 @@ def test_launcher_cwd_option_and_missing_script(tmp_path):
     assert r.returncode != 0 and "no such script" in r.stderr
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="needs the reference checkout")
+# stand-ins for the reference's modules, with the imports those make at top
+# level (ppo.py:6,11,21, ddqn.py:6,11,22, network.py:15,22, game.py:14,19,25)
+# and the names they read from the optional ones
+STANDINS = {
+    "game.py": "import wandb\nfrom IPython.display import clear_output\nfrom skimage.draw import line\n"
+               "class Game:\n    pass\n",
+    "network.py": "import torch\nfrom IPython.display import clear_output\nfrom torchviz import make_dot\n"
+                  "class MLP:\n    pass\nclass Value:\n    pass\nclass DMLP:\n    pass\n",
+    "ppo.py": "import torch\nfrom game import Game\nimport wandb\nfrom network import MLP, Value\n",
+    "ddqn.py": "import torch\nfrom game import Game\nimport wandb\nfrom network import MLP, Value, DMLP\n",
+}
+
+
 def test_reference_callers_resolve_to_facade(tmp_path):
-    """The reference's own ppo.py and ddqn.py, next to the reference's own
-    game.py (symlinked into a scratch directory, unchanged), imported by a
+    """Modules that import what the reference's ppo.py, ddqn.py and network.py
+    import at top level, next to a CPU game.py of their own, imported by a
     caller run through the launcher: `ppo.Game` and `ddqn.Game` are the
-    facade. Their optional imports (wandb, IPython, skimage, torchviz) are
-    stubbed because this image lacks them."""
+    facade. The optional imports (wandb, IPython, skimage, torchviz) are
+    stubbed where the image lacks them."""
     d = tmp_path / "ref"
     d.mkdir()
-    for f in os.listdir(REF):
-        if f.endswith((".py", ".json", ".csv", ".png")):
-            os.symlink(os.path.join(REF, f), d / f)
+    for f, text in STANDINS.items():
+        (d / f).write_text(text)
     (d / "lnw_check_callers.py").write_text(
         "import json, sys\nimport ppo, ddqn, game\n"
         "json.dump({'ppo': ppo.Game.__module__, 'ddqn': ddqn.Game.__module__,\n"
