@@ -425,6 +425,60 @@ typedef struct lnw_rollout_post_args {
 } lnw_rollout_post_args;
 int lnw_rollout_post(const lnw_rollout_post_args *args, void *stream);
 
+/* ---- fused acting step of the DDQN caller (DISCRETE mode) -------------------
+ * lnw_qnet_act replaces, per step and side, the reference DDQN loop's acting
+ * (ddqn.py:286-387): per live ship one batch-1 DMLP forward (network.py:246-305:
+ * the actor's conv head, x = [head(12), obs[49:]] with no LayerNorm, then the
+ * linear heads radar 2 / attack 5 / movement 50, each with bias and ReLU), three
+ * argmax().item() calls and Python `random` for epsilon-greedy
+ * (ddqn.py:299-308), for every env at once and written as the int32 rows lnw_step
+ * takes with LNW_ACT_I32. params: BatchedQNet.packed() (lnw/qlearn.py). One
+ * launch.
+ *  - LNW_QNET_EPS_GREEDY: with the four keyed uniforms u0..u3 of the row, explore
+ *    iff u0 < eps; the random row is [(int)(u1*2), (int)(u2*5), (int)(u3*50)]
+ *    (ddqn.py:300), else [argmax radar, argmax attack, argmax movement] with
+ *    torch.argmax's order (first maximal index; NaN above every number).
+ *    target_net is never put in eval() there, so its batch-1 calls normalise
+ *    with the row's own statistics: bn_running = 0.
+ *  - LNW_QNET_RED_RANDOM: untrained red (ddqn.py:316-328), no network: t < 20:
+ *    [(int)(u0*2), (int)(u1*2), 2 + (int)(u2*3)]; else [(int)(u0*2),
+ *    (u1 < red_aggression && tl_cnt > 0) ? 1 + (int)(u2*4) : 0, (int)(u3*50)].
+ *  - Rows of sunk ships (ddqn.py:312) and of envs with live == 0 are 0, 0, 0, 0;
+ *    column 3 is always 0.
+ *  - Keyed draws (as lnw_policy_act's): the uniforms of global row g = row_base +
+ *    e * n + i are lnw_fill_uniform_f32(seed, offset = (slot << 40) + 4 g), one
+ *    Philox block, so a shard draws what one call over all envs draws.
+ * The trained-red branch of the reference (ddqn.py:331) feeds the red network
+ * the last blue ship's state; here each side's network sees its own rows. */
+#define LNW_QNET_EPS_GREEDY 0
+#define LNW_QNET_RED_RANDOM 1
+typedef struct lnw_qnet_args {
+  const float *obs;            /* [E][n][D] this side's rows, 16-B aligned (RED_RANDOM: unread) */
+  int64_t E;
+  int32_t n, D, own0, A;       /* ships of the side, row length, first agent slot, agents per env */
+  int64_t obs_in_env_stride;   /* floats between envs' rows in obs (0: n * D) */
+  const float *params;         /* BatchedQNet.packed(): conv head 578 floats in lnw_actor_features'
+                                  order, then W [57][n_in] (radar, attack, movement rows), b [57] */
+  int32_t bn_running;          /* 0: per-row BatchNorm statistics, 1: running */
+  int32_t mode;                /* LNW_QNET_EPS_GREEDY, or LNW_QNET_RED_RANDOM (params may be NULL) */
+  float eps;
+  const float *eps_env;        /* NULL, or per-env epsilon [E] (eps unused) */
+  uint64_t seed, slot;         /* keyed draws: one slot per (step, side) */
+  int64_t row_base;            /* global id of row 0 (env_id_base * n) */
+  int32_t t;                   /* episode step (RED_RANDOM's < 20 switch) */
+  float red_aggression;
+  const uint16_t *tl_cnt;      /* RED_RANDOM: [A][E] the handle's LNW_F_TL_CNT field */
+  const uint8_t *alive;        /* [A][E] the handle's LNW_F_ALIVE field */
+  const uint8_t *live;         /* [E] episode still running (NULL: all) */
+  int32_t *full;               /* NULL, or [E][A][4] action array of lnw_step (LNW_ACT_I32): only rows
+                                  own0 .. own0 + n - 1 are written */
+  int32_t *act_out;            /* NULL, or replay rows of 4: env e ship i at e * act_env_stride + 4 i */
+  int64_t act_env_stride;
+  float *q_out;                /* NULL, or [E * n][57] the ReLU'd Q-values (EPS_GREEDY only) */
+  uint8_t *explored;           /* NULL, or [E * n]: 1 where a kept row took the random branch */
+} lnw_qnet_args;
+int lnw_qnet_act(const lnw_qnet_args *args, void *stream);
+
 /* Host-side constants the kernels use (for tests): hit probability tables
  * 1-(1-p)^n for p in {0.45, 0.63}, n = 0..8, in float64 and float32. */
 int lnw_hit_tables(double *tab64 /* [2][9] */, float *tab32 /* [2][9] */);

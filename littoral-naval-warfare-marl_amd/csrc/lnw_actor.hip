@@ -27,13 +27,9 @@ namespace {
 
 using namespace lnw;
 
-constexpr int WIN = 49;       // 7x7 terrain window
-constexpr float BN_EPS = 1e-5f;
+// the conv head (bn_relu, conv_head_win, conv_head_row) and its packed parameter layout
+#include "lnw_convhead.inc"
 
-// packed conv-head parameter layout (floats)
-constexpr int C1W = 0, C1B = 45, B1W = 50, B1B = 55, B1M = 60, B1V = 65;
-constexpr int C2W = 70, C2B = 430, B2W = 438, B2B = 446, B2M = 454, B2V = 462;
-constexpr int HW = 470, HB = 566, CONV_PARAMS = 578;  // then LayerNorm w, b [n_in] each
 constexpr int MAX_IN = 64;                            // n_in = obs_dim - 49 + 12 bound
 constexpr float LN_EPS = 1e-5f;
 
@@ -46,132 +42,12 @@ typedef double f64x4 __attribute__((ext_vector_type(4)));
 // load per 16 weights for the whole wave, instead of per-lane vector loads
 typedef const __attribute__((address_space(4))) float cfloat;
 
-// BatchNorm of one channel's n values: own statistics (biased variance) or
-// running ones, then the affine, then ReLU.
-template <int N>
-__device__ inline void bn_relu(float (&v)[N], const float *w, const float *b, const float *rm,
-                               const float *rv, int c, bool running) {
-  float mean, var;
-  if (running) {
-    mean = rm[c];
-    var = rv[c];
-  } else {
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < N; i++) s += v[i];
-    mean = s / (float)N;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < N; i++) q += (v[i] - mean) * (v[i] - mean);
-    var = q / (float)N;
-  }
-  const float inv = 1.0f / sqrtf(var + BN_EPS);
-#pragma unroll
-  for (int i = 0; i < N; i++) v[i] = fmaxf((v[i] - mean) * inv * w[c] + b[c], 0.f);
-}
-
 constexpr int CH_THREADS = 256;
 // lnw_policy_act's block (probe builds may change it: tools/build_probes.sh)
 #ifndef LNW_PA_THREADS
 #define LNW_PA_THREADS 512
 #endif
 constexpr int PA_THREADS = LNW_PA_THREADS;
-
-// The conv head of one row (network.py:70-82): conv 1->5 over the 7x7 window
-// win[0..48] (registers) -> BN -> ReLU -> 2x2 pool, conv 5->8 -> BN -> ReLU ->
-// pool, folded into the linear 8->12 (h). P: packed parameters in LDS
-// (broadcast reads); pc: the thread's column of a [45][stride] LDS parking area
-// for the pooled conv1 maps.
-__device__ __forceinline__ void conv_head_win(const float *P, const float (&win)[WIN], float *pc, int stride,
-                                              bool running, float (&h)[12]) {
-  // multiply-adds fused here (the build's -ffp-contract=off is for the step
-  // kernels' bit-exactness; the policy is held to the tolerance of fp32 torch,
-  // whose conv kernels fuse them too): half the VALU work of the head
-#pragma clang fp contract(fast)
-  // conv1 (1 -> 5, 3x3, pad 1) -> BN -> ReLU -> 2x2 max pool (7x7 -> 3x3),
-  // one channel at a time (rolled: 49 outputs live)
-#pragma unroll 1
-  for (int c = 0; c < 5; c++) {
-    float v[49];
-    const float *w = P + C1W + c * 9;
-#pragma unroll
-    for (int i = 0; i < 7; i++)
-#pragma unroll
-      for (int j = 0; j < 7; j++) {
-        float s = P[C1B + c];
-#pragma unroll
-        for (int ki = 0; ki < 3; ki++)
-#pragma unroll
-          for (int kj = 0; kj < 3; kj++) {
-            const int ii = i + ki - 1, jj = j + kj - 1;
-            if (ii >= 0 && ii < 7 && jj >= 0 && jj < 7) s += w[ki * 3 + kj] * win[ii * 7 + jj];
-          }
-        v[i * 7 + j] = s;
-      }
-    bn_relu<49>(v, P + B1W, P + B1B, P + B1M, P + B1V, c, running);
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-      for (int j = 0; j < 3; j++) {
-        const int r0 = 2 * i, c0 = 2 * j;
-        pc[(c * 9 + i * 3 + j) * stride] =
-            fmaxf(fmaxf(v[r0 * 7 + c0], v[r0 * 7 + c0 + 1]),
-                  fmaxf(v[(r0 + 1) * 7 + c0], v[(r0 + 1) * 7 + c0 + 1]));
-      }
-  }
-  // conv2 (5 -> 8, 3x3, pad 1) -> BN -> ReLU -> 2x2 max pool (3x3 -> 1x1),
-  // folded straight into the linear 8 -> 12 (convhead). Four output maps at a
-  // time accumulate while the input channels stream in from LDS one at a time
-  // (36 accumulators and 9 inputs live: the head then fits the kernel's
-  // registers without spilling; h sums the maps in the same order).
-#pragma unroll
-  for (int k = 0; k < 12; k++) h[k] = P[HB + k];
-#pragma unroll 1
-  for (int c0 = 0; c0 < 8; c0 += 4) {
-    float v2[4][9];
-#pragma unroll
-    for (int co = 0; co < 4; co++)
-#pragma unroll
-      for (int p = 0; p < 9; p++) v2[co][p] = P[C2B + c0 + co];
-#pragma unroll 1
-    for (int ci = 0; ci < 5; ci++) {
-      float pin[9];
-#pragma unroll
-      for (int k = 0; k < 9; k++) pin[k] = pc[(ci * 9 + k) * stride];
-#pragma unroll
-      for (int co = 0; co < 4; co++) {
-        const float *w = P + C2W + ((c0 + co) * 5 + ci) * 9;
-#pragma unroll
-        for (int i = 0; i < 3; i++)
-#pragma unroll
-          for (int j = 0; j < 3; j++)
-#pragma unroll
-            for (int ki = 0; ki < 3; ki++)
-#pragma unroll
-              for (int kj = 0; kj < 3; kj++) {
-                const int ii = i + ki - 1, jj = j + kj - 1;
-                if (ii >= 0 && ii < 3 && jj >= 0 && jj < 3) v2[co][i * 3 + j] += w[ki * 3 + kj] * pin[ii * 3 + jj];
-              }
-      }
-    }
-#pragma unroll
-    for (int co = 0; co < 4; co++) {
-      bn_relu<9>(v2[co], P + B2W, P + B2B, P + B2M, P + B2V, c0 + co, running);
-      const float f = fmaxf(fmaxf(v2[co][0], v2[co][1]), fmaxf(v2[co][3], v2[co][4]));
-#pragma unroll
-      for (int k = 0; k < 12; k++) h[k] += P[HW + k * 8 + c0 + co] * f;
-    }
-  }
-}
-
-// conv_head_win on a row in memory (features_kernel)
-__device__ __forceinline__ void conv_head_row(const float *P, const float *x, float *pc, int stride,
-                                              bool running, float (&h)[12]) {
-  float win[WIN];
-#pragma unroll
-  for (int i = 0; i < WIN; i++) win[i] = x[i];
-  conv_head_win(P, win, pc, stride, running, h);
-}
 
 // LayerNorm over [h, tail] (biased variance; tail = x[49:], n_in - 12 values)
 // with its affine, into u[0..n_in)

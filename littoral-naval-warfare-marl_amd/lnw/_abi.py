@@ -15,6 +15,7 @@ LNW_ACT_F32, LNW_ACT_F64, LNW_ACT_I32 = 0, 1, 2
 LNW_KIND_PYFLOAT, LNW_KIND_F32, LNW_KIND_F64 = 1, 2, 3
 LNW_RNG_PHILOX, LNW_RNG_TAPE = 0, 1
 LNW_OBS_ALL, LNW_OBS_BLUE, LNW_OBS_RED = -1, -2, -3
+LNW_QNET_EPS_GREEDY, LNW_QNET_RED_RANDOM = 0, 1
 LNW_ERRF_ZERODIV, LNW_ERRF_NAN_ROUND, LNW_ERRF_TAPE, LNW_ERRF_MISSILES = 1, 2, 4, 8
 
 (F_POS, F_RADAR, F_MISSILES, F_MKIND, F_ALIVE, F_TYPE, F_STEPS, F_DIST_LZ, F_TL_CNT, F_TL,
@@ -30,7 +31,7 @@ SYMBOLS = [
     "lnw_los_batch", "lnw_astar_batch", "lnw_move_batch", "lnw_path_query", "lnw_los_query", "lnw_copy",
     "lnw_fill_uniform_f32", "lnw_hit_tables", "lnw_set_analytics", "lnw_actor_features",
     "lnw_state_bytes", "lnw_get_state", "lnw_set_state", "lnw_step_kernel",
-    "lnw_policy_act", "lnw_rollout_post",
+    "lnw_policy_act", "lnw_rollout_post", "lnw_qnet_act",
 ]
 
 # lnw_step_kernel codes (include/lnw.h LNW_KERNEL_*)
@@ -90,6 +91,18 @@ class RolloutPostArgs(C.Structure):  # include/lnw.h: lnw_rollout_post_args
                 ("running_env_stride", C.c_int64), ("stop_at_done", C.c_int32)]
 
 
+class QnetArgs(C.Structure):  # include/lnw.h: lnw_qnet_args
+    _fields_ = [("obs", C.c_void_p), ("E", C.c_int64),
+                ("n", C.c_int32), ("D", C.c_int32), ("own0", C.c_int32), ("A", C.c_int32),
+                ("obs_in_env_stride", C.c_int64), ("params", C.c_void_p),
+                ("bn_running", C.c_int32), ("mode", C.c_int32), ("eps", C.c_float),
+                ("eps_env", C.c_void_p), ("seed", C.c_uint64), ("slot", C.c_uint64),
+                ("row_base", C.c_int64), ("t", C.c_int32), ("red_aggression", C.c_float),
+                ("tl_cnt", C.c_void_p), ("alive", C.c_void_p), ("live", C.c_void_p),
+                ("full", C.c_void_p), ("act_out", C.c_void_p), ("act_env_stride", C.c_int64),
+                ("q_out", C.c_void_p), ("explored", C.c_void_p)]
+
+
 class LnwError(RuntimeError):
     pass
 
@@ -142,6 +155,7 @@ def load(path=None):
         "lnw_step_kernel": ([P], C.c_int),
         "lnw_policy_act": ([C.POINTER(PolicyArgs), P], C.c_int),
         "lnw_rollout_post": ([C.POINTER(RolloutPostArgs), P], C.c_int),
+        "lnw_qnet_act": ([C.POINTER(QnetArgs), P], C.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
