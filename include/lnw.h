@@ -479,6 +479,59 @@ typedef struct lnw_qnet_args {
 } lnw_qnet_args;
 int lnw_qnet_act(const lnw_qnet_args *args, void *stream);
 
+/* ---- DDQN learner step ------------------------------------------------------
+ * lnw_qnet_grad is the reference's optimize() (ddqn.py:153-247) for one side on
+ * `rows` transitions, up to the gradient: the target network's forward on
+ * next_state with BatchNorm batch statistics (it is never put in eval()), y =
+ * float32(double(float32(gamma * per-head max) * done) + reward); the policy
+ * network's forward on state (batch statistics, or the running ones:
+ * policy_bn_running, what the reference's red side does), the three Q-values
+ * gathered at action[0..2], loss = mean((qs - y)^2) over the 3 * rows elements,
+ * and its gradient by every policy parameter — through the ReLU, the linear
+ * heads, convhead, both max pools (first maximum of a window in row-major
+ * order, as torch), both BatchNorms (with the batch-mean terms under batch
+ * statistics) and both convolutions. grad has BatchedQNet.packed()'s layout,
+ * zeros in the four running-statistics slots, and is not clamped. Every
+ * training-mode forward updates that network's running statistics in its
+ * parameter vector (momentum 0.1, unbiased variance) unless freeze_running.
+ * A chain of launches on `stream`: no host synchronisation, no allocation, no
+ * atomics (bitwise reproducible). workspace: lnw_qlearn_workspace_bytes(rows, D)
+ * bytes, 16-B aligned (0 for unsupported shapes).
+ * Limits as lnw_qnet_act: 16-B aligned rows, D % 4 == 0, 49 <= D, D - 37 <= 64.
+ *
+ * lnw_qnet_adam clamps the gradient to [-clamp, clamp] (clamp > 0) and applies
+ * one torch.optim.Adam step (no weight decay) to all `count` elements; the step
+ * number is *step_dev + 1, a device counter the call advances, so a captured
+ * graph replays with the right bias correction. A zero gradient with zero
+ * moments leaves the parameter bit-unchanged (the running-statistics slots). */
+typedef struct lnw_qlearn_args {
+  const float *state;          /* [rows][D], 16-B aligned */
+  const float *next_state;     /* [rows][D], 16-B aligned */
+  int64_t rows;
+  int32_t D;
+  int32_t action_stride;       /* int32s between rows of action (>= 3) */
+  const int32_t *action;       /* row r: action[r * action_stride + 0..2] = radar, attack, movement */
+  const void *reward;          /* [rows] float32, or float64 with reward_f64 */
+  const int32_t *done;         /* [rows] 1 while the episode runs */
+  int32_t reward_f64;
+  int32_t policy_bn_running;   /* 0: policy BatchNorm on batch statistics, 1: running */
+  int32_t freeze_running;      /* 1: leave the running statistics alone */
+  float gamma;
+  float *policy_params;        /* BatchedQNet.packed() layout; running statistics updated in place */
+  float *target_params;
+  float *grad;                 /* [578 + 57 * n_in + 57] out */
+  float *loss;                 /* [1] out */
+  float *y_out;                /* NULL, or [rows][3] */
+  float *qs_out;               /* NULL, or [rows][3] */
+  float *stats_out;            /* NULL, or [2 policy, target][2 mean, biased var][13 channels: conv1 5, conv2 8] */
+  void *workspace;
+  int64_t workspace_bytes;
+} lnw_qlearn_args;
+int64_t lnw_qlearn_workspace_bytes(int64_t rows, int32_t D);
+int lnw_qnet_grad(const lnw_qlearn_args *args, void *stream);
+int lnw_qnet_adam(float *params, const float *grad, float *m, float *v, int64_t count, int64_t *step_dev,
+                  float lr, float beta1, float beta2, float eps, float clamp, void *stream);
+
 /* Host-side constants the kernels use (for tests): hit probability tables
  * 1-(1-p)^n for p in {0.45, 0.63}, n = 0..8, in float64 and float32. */
 int lnw_hit_tables(double *tab64 /* [2][9] */, float *tab32 /* [2][9] */);

@@ -32,6 +32,7 @@ SYMBOLS = [
     "lnw_fill_uniform_f32", "lnw_hit_tables", "lnw_set_analytics", "lnw_actor_features",
     "lnw_state_bytes", "lnw_get_state", "lnw_set_state", "lnw_step_kernel",
     "lnw_policy_act", "lnw_rollout_post", "lnw_qnet_act",
+    "lnw_qlearn_workspace_bytes", "lnw_qnet_grad", "lnw_qnet_adam",
 ]
 
 # lnw_step_kernel codes (include/lnw.h LNW_KERNEL_*)
@@ -103,6 +104,16 @@ class QnetArgs(C.Structure):  # include/lnw.h: lnw_qnet_args
                 ("q_out", C.c_void_p), ("explored", C.c_void_p)]
 
 
+class QlearnArgs(C.Structure):  # include/lnw.h: lnw_qlearn_args
+    _fields_ = [("state", C.c_void_p), ("next_state", C.c_void_p), ("rows", C.c_int64),
+                ("D", C.c_int32), ("action_stride", C.c_int32), ("action", C.c_void_p),
+                ("reward", C.c_void_p), ("done", C.c_void_p), ("reward_f64", C.c_int32),
+                ("policy_bn_running", C.c_int32), ("freeze_running", C.c_int32), ("gamma", C.c_float),
+                ("policy_params", C.c_void_p), ("target_params", C.c_void_p), ("grad", C.c_void_p),
+                ("loss", C.c_void_p), ("y_out", C.c_void_p), ("qs_out", C.c_void_p),
+                ("stats_out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 class LnwError(RuntimeError):
     pass
 
@@ -156,6 +167,10 @@ def load(path=None):
         "lnw_policy_act": ([C.POINTER(PolicyArgs), P], C.c_int),
         "lnw_rollout_post": ([C.POINTER(RolloutPostArgs), P], C.c_int),
         "lnw_qnet_act": ([C.POINTER(QnetArgs), P], C.c_int),
+        "lnw_qlearn_workspace_bytes": ([I64, I32], C.c_int64),
+        "lnw_qnet_grad": ([C.POINTER(QlearnArgs), P], C.c_int),
+        "lnw_qnet_adam": ([P, P, P, P, I64, P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, P],
+                          C.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)

@@ -19,7 +19,7 @@ OUT = os.path.join(HERE, "liblnw.so")
 DIAG_OUT = os.path.join(HERE, "liblnw_diag.so")
 DIAG_DEFINES = ("LNW_DIAG", "LNW_GROUP_PROF")
 SOURCES = [os.path.join(CSRC, "lnw_kernels.hip"), os.path.join(CSRC, "lnw_actor.hip"),
-           os.path.join(CSRC, "lnw_qnet.hip")]
+           os.path.join(CSRC, "lnw_qnet.hip"), os.path.join(CSRC, "lnw_qlearn.hip")]
 DEPS = SOURCES + [os.path.join(CSRC, "lnw_device.h"), os.path.join(CSRC, "lnw_quiet.inc"),
                   os.path.join(CSRC, "lnw_group.inc"), os.path.join(CSRC, "lnw_convhead.inc"),
                   os.path.join(INCLUDE, "lnw.h")]

@@ -4,8 +4,9 @@ and untrained-red random actions from keyed Philox draws, and a transition
 collector that fills a device replay ring. Observations never leave the GPU.
 
 Reference: network.py:246-305 (DMLP), ddqn.py:149-151 (get_epsilon),
-ddqn.py:286-387 (acting), ddqn.py:175-193 (the TD target of optimize()).
-The optimiser step and replay prioritisation stay with the caller.
+ddqn.py:286-387 (acting), ddqn.py:153-247 (optimize(): QLearner, the TD loss,
+its gradient and the clamped Adam step as HIP kernels, csrc/lnw_qlearn.hip).
+Replay prioritisation stays with the caller.
 """
 import ctypes as C
 import math
@@ -109,13 +110,28 @@ class BatchedQNet(nn.Module):
         """Every parameter lnw_qnet_act reads (csrc/lnw_qnet.hip), in its order:
         the conv head in lnw_actor_features' order (578 floats), then W [57][n_in]
         with the rows in radar, attack, movement order, then b [57]."""
-        parts = [self.conv1.weight, self.conv1.bias, self.norm1.weight, self.norm1.bias,
-                 self.norm1.running_mean, self.norm1.running_var, self.conv2.weight,
-                 self.conv2.bias, self.norm2.weight, self.norm2.bias, self.norm2.running_mean,
-                 self.norm2.running_var, self.convhead.weight, self.convhead.bias,
-                 self.radar.weight, self.attack.weight, self.movement.weight,
-                 self.radar.bias, self.attack.bias, self.movement.bias]
-        return torch.cat([p.detach().reshape(-1).float() for p in parts]).contiguous()
+        return torch.cat([p.detach().reshape(-1).float() for p in self._pack_order()]).contiguous()
+
+    def _pack_order(self):
+        return [self.conv1.weight, self.conv1.bias, self.norm1.weight, self.norm1.bias,
+                self.norm1.running_mean, self.norm1.running_var, self.conv2.weight,
+                self.conv2.bias, self.norm2.weight, self.norm2.bias, self.norm2.running_mean,
+                self.norm2.running_var, self.convhead.weight, self.convhead.bias,
+                self.radar.weight, self.attack.weight, self.movement.weight,
+                self.radar.bias, self.attack.bias, self.movement.bias]
+
+    @torch.no_grad()
+    def unpack_(self, flat):
+        """The inverse of packed(): load a flat vector in its layout into the
+        parameters and running statistics, in place."""
+        parts = self._pack_order()
+        if flat.numel() != sum(p.numel() for p in parts):
+            raise ValueError("flat vector length does not match packed()")
+        k = 0
+        for p in parts:
+            p.copy_(flat[k:k + p.numel()].reshape(p.shape).to(p.device, p.dtype))
+            k += p.numel()
+        return self
 
     @staticmethod
     def _bn(m, z, bn):
@@ -320,10 +336,18 @@ class QCollector:
         self.t = 0          # episode step of untrained red's switch
         self._bp = self._rp = None
 
-    def refresh_params(self):
-        """Re-pack the networks' parameters (after a learner update)."""
+    def refresh_params(self, params=None):
+        """Re-pack the networks' parameters (after a learner update). params: a
+        flat device vector in packed() layout for the learning side's network
+        (QLearner.target_params, what the reference acts with, ddqn.py:303): it
+        is read in place at every step, so later updates need no repack."""
         self._bp = self.blue_net.packed()
         self._rp = self.red.packed() if isinstance(self.red, BatchedQNet) else None
+        if params is not None:
+            if self.side == "blue":
+                self._bp = params
+            else:
+                self._rp = params
 
     def new_episode(self):
         """Restart untrained red's episode-step count (after a reset())."""
@@ -389,3 +413,265 @@ class QCollector:
         flat = lambda t: t.reshape((self.cap * E,) + tuple(t.shape[2:]))  # noqa: E731
         return dict(state=flat(self.state)[idx], action=flat(self.action)[idx], reward=flat(self.reward)[idx],
                     next_state=flat(self.next_state)[idx], done=flat(self.done)[idx], index=idx)
+
+
+# names of packed()'s segments, in its order (state_dict keys)
+PACKED_NAMES = ("conv1.weight", "conv1.bias", "norm1.weight", "norm1.bias", "norm1.running_mean",
+                "norm1.running_var", "conv2.weight", "conv2.bias", "norm2.weight", "norm2.bias",
+                "norm2.running_mean", "norm2.running_var", "convhead.weight", "convhead.bias",
+                "radar.weight", "attack.weight", "movement.weight", "radar.bias", "attack.bias",
+                "movement.bias")
+_RUNNING = ("norm1.running_mean", "norm1.running_var", "norm2.running_mean", "norm2.running_var")
+
+
+def packed_slices(n_in):
+    """{state_dict name: (offset, shape)} of packed()'s layout for n_in head inputs."""
+    shapes = ((5, 1, 3, 3), (5,), (5,), (5,), (5,), (5,), (8, 5, 3, 3), (8,), (8,), (8,), (8,), (8,),
+              (12, 8), (12,), (N_RADAR, n_in), (N_ATTACK, n_in), (N_MOVE, n_in), (N_RADAR,),
+              (N_ATTACK,), (N_MOVE,))
+    out, k = {}, 0
+    for name, shp in zip(PACKED_NAMES, shapes):
+        out[name] = (k, shp)
+        k += int(np.prod(shp))
+    return out
+
+
+def _flat_forward(theta, obs, bn, sl):
+    """DMLP.forward from a flat parameter vector (differentiable in theta):
+    q [B, 57] after the ReLU, and the batch mean / biased variance of the 13
+    BatchNorm channels [2, 13]. bn: "batch" or "running" (the running slots are
+    constants then)."""
+    def seg(name):
+        k, shp = sl[name]
+        t = theta[k:k + int(np.prod(shp))].reshape(shp)
+        return t.detach() if name in _RUNNING else t
+
+    B = obs.shape[0]
+    stats = []
+
+    def norm(z, pre):
+        mean, var = z.mean((0, 2, 3)), z.var((0, 2, 3), unbiased=False)
+        stats.append((mean.detach(), var.detach()))
+        if bn == "batch":
+            return F.batch_norm(z, None, None, seg(pre + ".weight"), seg(pre + ".bias"), True, 0.0, 1e-5)
+        return F.batch_norm(z, seg(pre + ".running_mean"), seg(pre + ".running_var"), seg(pre + ".weight"),
+                            seg(pre + ".bias"), False, 0.0, 1e-5)
+
+    z = obs[:, :WINDOW].reshape(B, 1, 7, 7)
+    z = F.max_pool2d(F.relu(norm(F.conv2d(z, seg("conv1.weight"), seg("conv1.bias"), padding=1), "norm1")), 2, 2)
+    z = F.max_pool2d(F.relu(norm(F.conv2d(z, seg("conv2.weight"), seg("conv2.bias"), padding=1), "norm2")), 2, 2)
+    x = torch.cat((F.linear(torch.flatten(z, 1), seg("convhead.weight"), seg("convhead.bias")), obs[:, WINDOW:]), 1)
+    q = torch.cat([F.relu(F.linear(x, seg(h + ".weight"), seg(h + ".bias"))) for h in ("radar", "attack", "movement")], 1)
+    st = torch.stack([torch.cat([stats[0][0], stats[1][0]]), torch.cat([stats[0][1], stats[1][1]])])
+    return q, st
+
+
+class QLearner:
+    """The learner half of the DDQN loop: ddqn.py:153-247 `optimize()` for one
+    side, on flat device vectors in BatchedQNet.packed() layout.
+
+    `theta` (`.params`) and `theta_target` (`.target_params`) hold the policy and
+    target networks, `m`, `v` and a device step counter the Adam state. `target`
+    None starts the target as a copy of the policy. policy_bn: "batch" — the
+    policy forward and backward on batch statistics (the reference's blue side);
+    "running" — on the running statistics (what the reference's red side does:
+    ddqn.py:212 puts red_policy_net in eval() and ddqn.py:222 calls train() on
+    the other network). The target network always runs on batch statistics, and
+    every training-mode forward updates that network's running statistics.
+
+    impl="hip": lnw_qnet_grad + lnw_qnet_adam (csrc/lnw_qlearn.hip), a chain of
+    launches on the current stream with no host synchronisation; capturable in
+    a torch.cuda.graph. impl="torch": the same steps with torch ops, autograd and
+    torch.optim.Adam on the same flat state, on the host or the device — the arm
+    the kernels are tested and timed against.
+
+    batch: what QCollector.sample() returns ([B, n, ...] is flattened to rows and
+    `done` repeated per ship), or a dict of row tensors state [B, D], action
+    [B, >= 3], reward [B] (float32 or float64), next_state [B, D], done [B]."""
+
+    def __init__(self, policy, target=None, lr=1e-4, gamma=0.99, betas=(0.9, 0.999), eps=1e-8, clamp=1.0,
+                 policy_bn="batch", impl="hip", device=None):
+        if policy_bn not in ("batch", "running"):
+            raise ValueError("policy_bn must be 'batch' or 'running'")
+        if impl not in ("hip", "torch"):
+            raise ValueError("impl must be 'hip' or 'torch'")
+        if device is None:
+            device = "cuda" if impl == "hip" else next(policy.parameters()).device
+        self.device = dev = torch.device(device)
+        if impl == "hip" and dev.type != "cuda":
+            raise ValueError("impl='hip' needs a GPU device")
+        self.policy, self.target = policy, target
+        self.lr, self.gamma, self.betas, self.eps, self.clamp = float(lr), float(gamma), tuple(betas), float(eps), float(clamp)
+        self.policy_bn, self.impl = policy_bn, impl
+        self.D, self.n_in = policy.obs_dim, policy.n_in
+        self.slices = packed_slices(self.n_in)
+        self.theta = policy.packed().to(dev)
+        self.theta_target = (policy if target is None else target).packed().to(dev)
+        self.m, self.v = torch.zeros_like(self.theta), torch.zeros_like(self.theta)
+        self.step_count = torch.zeros(1, dtype=torch.int64, device=dev)
+        # num_batches_tracked of [policy, target]
+        src_t = policy if target is None else target
+        self.nbt = torch.tensor([int(policy.norm1.num_batches_tracked), int(src_t.norm1.num_batches_tracked)],
+                                dtype=torch.int64, device=dev)
+        self._nbt_inc = torch.tensor([int(policy_bn == "batch"), 1], dtype=torch.int64, device=dev)
+        self._grad = torch.zeros_like(self.theta)
+        self._loss = torch.zeros(1, dtype=torch.float32, device=dev)
+        self._ws = None
+        self._opt = None
+
+    @property
+    def params(self):
+        return self.theta
+
+    @property
+    def target_params(self):
+        return self.theta_target
+
+    def rows(self, batch):
+        """The batch as contiguous row tensors on the learner's device."""
+        dev = self.device
+        st, ns = batch["state"], batch["next_state"]
+        ac, rw, dn = batch["action"], batch["reward"], batch["done"]
+        if st.dim() == 3:
+            n = st.shape[1]
+            dn = dn[:, None].expand(dn.shape[0], n).reshape(-1)
+            st, ns = st.reshape(-1, st.shape[-1]), ns.reshape(-1, ns.shape[-1])
+            ac, rw = ac.reshape(-1, ac.shape[-1]), rw.reshape(-1)
+        if rw.dtype != torch.float64:
+            rw = rw.float()
+        return dict(state=st.to(dev, torch.float32).contiguous(), next_state=ns.to(dev, torch.float32).contiguous(),
+                    action=ac.to(dev, torch.int32).contiguous(), reward=rw.to(dev).contiguous(),
+                    done=dn.to(dev, torch.int32).contiguous())
+
+    # ---- HIP arm ---------------------------------------------------------------
+    def _grad_hip(self, r, want, freeze):
+        from . import _abi
+        L = _abi.load()
+        dev = self.device
+        B, D = r["state"].shape
+        need = L.lnw_qlearn_workspace_bytes(B, D)
+        if need <= 0:
+            raise _abi.LnwError(f"lnw_qnet_grad does not support rows={B}, D={D}")
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        a = _abi.QlearnArgs()
+        a.state, a.next_state, a.rows, a.D = r["state"].data_ptr(), r["next_state"].data_ptr(), B, D
+        a.action, a.action_stride = r["action"].data_ptr(), r["action"].shape[1]
+        a.reward, a.reward_f64 = r["reward"].data_ptr(), int(r["reward"].dtype == torch.float64)
+        a.done = r["done"].data_ptr()
+        a.policy_bn_running, a.freeze_running, a.gamma = int(self.policy_bn == "running"), int(freeze), self.gamma
+        a.policy_params, a.target_params = self.theta.data_ptr(), self.theta_target.data_ptr()
+        a.grad, a.loss = self._grad.data_ptr(), self._loss.data_ptr()
+        out = {}
+        if want:
+            out["y"] = torch.empty((B, 3), dtype=torch.float32, device=dev)
+            out["qs"] = torch.empty((B, 3), dtype=torch.float32, device=dev)
+            out["stats"] = torch.empty((2, 2, 13), dtype=torch.float32, device=dev)
+            a.y_out, a.qs_out, a.stats_out = out["y"].data_ptr(), out["qs"].data_ptr(), out["stats"].data_ptr()
+        a.workspace, a.workspace_bytes = self._ws.data_ptr(), self._ws.numel()
+        _abi.check(L.lnw_qnet_grad(C.byref(a), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        return out
+
+    def _adam_hip(self):
+        from . import _abi
+        L = _abi.load()
+        _abi.check(L.lnw_qnet_adam(self.theta.data_ptr(), self._grad.data_ptr(), self.m.data_ptr(),
+                                   self.v.data_ptr(), self.theta.numel(), self.step_count.data_ptr(),
+                                   self.lr, self.betas[0], self.betas[1], self.eps, self.clamp,
+                                   C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+
+    # ---- torch arm ---------------------------------------------------------------
+    def _update_running(self, theta, stats, B):
+        with torch.no_grad():
+            for pre, lo, hi, n in (("norm1", 0, 5, 49 * B), ("norm2", 5, 13, 9 * B)):
+                for name, val in ((pre + ".running_mean", stats[0, lo:hi]),
+                                  (pre + ".running_var", stats[1, lo:hi] * (n / (n - 1.0)))):
+                    k, shp = self.slices[name]
+                    seg = theta[k:k + shp[0]]
+                    seg.copy_(0.1 * val + 0.9 * seg)
+
+    def _grad_torch(self, r, freeze):
+        B = r["state"].shape[0]
+        sl = self.slices
+        with torch.no_grad():
+            qt, st_t = _flat_forward(self.theta_target, r["next_state"], "batch", sl)
+            nxt = torch.stack([qt[:, lo:hi].max(1).values for lo, hi in HEADS], 1)
+            t = (self.gamma * nxt) * r["done"][:, None]
+            y = (t + r["reward"][:, None]).float()  # (float64 rewards: the sum in float64, then float32)
+        th = self.theta.detach().clone().requires_grad_(True)
+        q, st_p = _flat_forward(th, r["state"], self.policy_bn, sl)
+        act = r["action"].long()
+        qs = torch.stack([q[:, lo:hi].gather(1, act[:, h:h + 1].clamp(0, hi - lo - 1))[:, 0]
+                          for h, (lo, hi) in enumerate(HEADS)], 1)
+        loss = F.mse_loss(qs, y)
+        loss.backward()
+        self._grad.copy_(th.grad)
+        self._loss.copy_(loss.detach().reshape(1))
+        if not freeze:
+            self._update_running(self.theta_target, st_t, B)
+            if self.policy_bn == "batch":
+                self._update_running(self.theta, st_p, B)
+        return dict(y=y, qs=qs.detach(), stats=torch.stack([st_p, st_t]))
+
+    def _adam_torch(self):
+        if self._opt is None:
+            self._p = nn.Parameter(self.theta)  # (shares theta's storage)
+            self._opt = torch.optim.Adam([self._p], lr=self.lr, betas=self.betas, eps=self.eps)
+            st = self._opt.state[self._p]
+            st["step"], st["exp_avg"], st["exp_avg_sq"] = torch.tensor(0.0), self.m, self.v
+        g = self._grad.clone()
+        if self.clamp > 0:
+            g.clamp_(-self.clamp, self.clamp)
+        self._p.grad = g
+        self._opt.step()
+        self.step_count += 1
+
+    # ---- public ----------------------------------------------------------------
+    def grad(self, batch, update_running=True):
+        """Loss and gradient of one batch, without the optimiser step: dict(loss
+        0-d, grad [P] unclamped in packed() layout, y [B, 3], qs [B, 3], stats
+        [2 policy / target, 2 mean / biased variance, 13 channels]). The
+        training-mode forwards update the running statistics (and the batch
+        counters) as the reference's do, unless update_running is False."""
+        r = self.rows(batch)
+        if self.impl == "hip":
+            out = self._grad_hip(r, True, not update_running)
+        else:
+            out = self._grad_torch(r, not update_running)
+        if update_running:
+            self.nbt += self._nbt_inc
+        out["loss"], out["grad"] = self._loss.reshape(()).clone(), self._grad.clone()
+        return out
+
+    def step(self, batch):
+        """One optimize(): gradient, clamp, Adam. Returns the loss, a 0-d device
+        tensor (nothing synchronises with the host)."""
+        r = self.rows(batch)
+        if self.impl == "hip":
+            self._grad_hip(r, False, False)
+            self._adam_hip()
+        else:
+            self._grad_torch(r, False)
+            self._adam_torch()
+        self.nbt += self._nbt_inc
+        return self._loss.reshape(()).clone()
+
+    @torch.no_grad()
+    def sync_target(self):
+        """target.load_state_dict(policy.state_dict()) (ddqn.py:442): parameters,
+        running statistics and the batch counter."""
+        self.theta_target.copy_(self.theta)
+        self.nbt[1:2] = self.nbt[0:1]
+
+    @torch.no_grad()
+    def export(self):
+        """Write the vectors and num_batches_tracked back into the BatchedQNet
+        modules (the target only if one was given); returns (policy, target)."""
+        nbt = self.nbt.cpu()
+        for net, flat, k in ((self.policy, self.theta, 0), (self.target, self.theta_target, 1)):
+            if net is None:
+                continue
+            net.unpack_(flat.detach().cpu())
+            for nm in (net.norm1, net.norm2):
+                nm.num_batches_tracked.fill_(int(nbt[k]))
+        return self.policy, self.target
