@@ -186,21 +186,32 @@ def test_adam_three_steps_and_clamp():
     assert torch.allclose(m2, torch.full((8,), 5.0, device="cuda"))
 
 
-@pytest.mark.parametrize("D", [52, 68, 84])
-@pytest.mark.parametrize("B", [1, 3, 64, 600])
-@pytest.mark.parametrize("policy_bn", ["batch", "running"])
+SHAPE_CASES = [(bn, B, D) for bn in ("batch", "running") for B in (1, 3, 64, 600) for D in (52, 68, 72, 84, 100)]
+SHAPE_CASES.append(("batch", 8321, 68))
+
+
+@pytest.mark.parametrize("policy_bn,B,D", SHAPE_CASES, ids=[f"{bn}-{B}-{D}" for bn, B, D in SHAPE_CASES])
 def test_shapes_against_torch_arm(B, D, policy_bn):
     """.grad of the kernels against the torch arm on the device, both under the
     float64 oracle's bound: B = 600 spans several workgroups with a partial last
-    one, D = 52 / 68 / 84 are n_in 15 / 31 / 47 (both head widths), B = 1 and 3
-    the smallest batches torch's training-mode BatchNorm accepts."""
+    one, D = 52 / 68 / 84 are n_in 15 / 31 / 47 (both head widths), D = 72 and
+    100 are n_in 35 and 63, the narrowest and the widest row of the 64-wide
+    path (63 of the head-gradient kernel's 64 lanes), B = 1 and 3 the smallest
+    batches torch's training-mode BatchNorm accepts. B = 8321 is 66 workgroups,
+    the last holding one row: the reduction kernels' loop over the workgroups'
+    partials (one per lane) makes a second trip. That case takes its float32
+    arm on the host, as test_grad_matches_reference_and_float64 does: the
+    device arm's first convolution at a new batch size this large spends about
+    20 s in the library's kernel search, the host arm 0.03 s."""
     from lnw.qlearn import QLearner
     pol, tgt = random_net(D, 100 + D), random_net(D, 200 + D)
     batch = random_batch(B, D, 7 * B + D)
+    host = {k: v.cpu() for k, v in batch.items()}
+    arm = "cuda" if B <= 600 else "cpu"
     H = QLearner(pol, tgt, policy_bn=policy_bn)
-    T = QLearner(pol, tgt, policy_bn=policy_bn, impl="torch", device="cuda")
-    o64 = oracle64(H.theta, H.theta_target, {k: v.cpu() for k, v in batch.items()}, 0.99, policy_bn)
-    out, ref = H.grad(batch), T.grad(batch)
+    T = QLearner(pol, tgt, policy_bn=policy_bn, impl="torch", device=arm)
+    o64 = oracle64(H.theta, H.theta_target, host, 0.99, policy_bn)
+    out, ref = H.grad(batch), T.grad(batch if arm == "cuda" else host)
     for name in ("y", "qs", "loss"):
         check(name, out[name], ref[name], o64[name])
     for i in range(2):

@@ -122,7 +122,9 @@ def test_kernel_matches_reference(gold, prefix, n, mode, bn):
 
 
 # ---------------------------------------------------------------- self-consistency
-SHAPES = [(37, 3, 64), (300, 4, 68), (5, 8, 84)]  # ragged wave; blocks + tail; NI = 64
+# ragged wave; blocks + tail; NI = 64; then the 64-wide path's edges: n_in = 35 (the smallest
+# width on it) and n_in = 63 (the largest accepted)
+SHAPES = [(37, 3, 64), (300, 4, 68), (5, 8, 84), (70, 5, 72), (9, 12, 100)]
 
 
 @pytest.mark.parametrize("E,n,D", SHAPES)

@@ -176,7 +176,8 @@ def test_policy_packing_matches_layers():
     import torch
     from lnw.rollout import BatchedActor, BatchedCritic
     torch.manual_seed(5)
-    for D, nb in ((68, 4), (60, 2)):
+    # (72, 5), (84, 8), (100, 12): n_in > 32, two fc1 k-pairs; critic dq 5, 6, 7
+    for D, nb in ((68, 4), (60, 2), (72, 5), (84, 8), (100, 12)):
         a = BatchedActor.for_obs(D)
         n_in = D - 49 + 12
         P = a.packed_policy().numpy()
@@ -228,3 +229,25 @@ def test_policy_packing_matches_layers():
         h = np.tanh(h @ W2c.T + b2)
         h = np.tanh(h @ W3c.T + b3)
         np.testing.assert_allclose(h @ w4 + b4, want, atol=1e-5)
+
+
+def test_net_oracle_cases_hold_on_the_host():
+    """tests/_net_oracle.py on the host alone, at every shape the GPU tests of
+    test_gpu_net_shapes.py use: building a case asserts that the float32 arm
+    meets the tolerance against float64 and that a wrongly wired float64
+    network differs by more than 100 tolerances; the margins are printed."""
+    import _net_oracle as O
+    for n in (2, 5, 8, 12):
+        for bn in ("sample", "running"):
+            c = O.features_case(n, bn)
+            print(f"features n={n} {bn}: err_ref {O.max_abs(c['ref'], c['want']):.3e}")
+    for n in (4, 5, 8, 12):
+        for bn in ("sample", "running"):
+            c = O.policy_case(n, bn)
+            assert len(c["moved"]) == (1 if n == 4 else 3)
+            print(f"policy n={n} {bn}: err_ref {O.max_abs(c['ref'], c['want']):.3e}, "
+                  f"|log p| <= {float(c['want'].abs().max()):.2f}, moved {c['moved']}")
+    for n, D in ((1, 56), (2, 60), (3, 64), (4, 68), (5, 72), (8, 84), (12, 100), (16, 100)):
+        c = O.critic_case(n, D)
+        assert (c["moved"] is None) == (n == 1)
+        print(f"critic n={n} D={D}: err_ref {O.max_abs(c['ref'], c['want']):.3e}, moved {c['moved']}")
