@@ -27,27 +27,19 @@ namespace {
 
 using namespace lnw;
 
-// the conv head (bn_relu, conv_head_win, conv_head_row) and its packed parameter layout
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+
+// the conv head (bn_relu, conv_head_win, conv_head_row, load_tail_q), its packed
+// parameter layout and the supported observation width (MAX_IN, obs_width_ok)
 #include "lnw_convhead.inc"
 
-constexpr int MAX_IN = 64;                            // n_in = obs_dim - 49 + 12 bound
 constexpr float LN_EPS = 1e-5f;
 
 extern __shared__ float actor_lds[];
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-// read-only parameters through the constant address space: wave-uniform
-// indices then become scalar loads (s_load / s_buffer_load) into SGPRs, one
-// load per 16 weights for the whole wave, instead of per-lane vector loads
-typedef const __attribute__((address_space(4))) float cfloat;
-
 constexpr int CH_THREADS = 256;
-// lnw_policy_act's block (probe builds may change it: tools/build_probes.sh)
-#ifndef LNW_PA_THREADS
-#define LNW_PA_THREADS 512
-#endif
-constexpr int PA_THREADS = LNW_PA_THREADS;
+constexpr int PA_THREADS = 512;  // lnw_policy_act's block
 
 // LayerNorm over [h, tail] (biased variance; tail = x[49:], n_in - 12 values)
 // with its affine, into u[0..n_in)
@@ -75,22 +67,6 @@ template <int NT>
 __device__ __forceinline__ void load_tail(const float *x, int D, float (&tl)[NT]) {
 #pragma unroll
   for (int k = 0; k < NT; k++) tl[k] = x[WIN + k < D ? WIN + k : D - 1];
-}
-
-// The same for a 16-B aligned row of D % 4 == 0 floats (lnw_policy_act checks
-// both): the float4 quads from x[48] on, one dwordx4 per quad instead of one
-// dword load per value (quad indices clamped into the row; the values past
-// n_in - 12 they duplicate are unused)
-template <int NT>
-__device__ __forceinline__ void load_tail_q(const float *x, int D, float (&tl)[NT]) {
-  constexpr int NQ = (NT + 1 + 3) / 4;  // x[48] .. x[48 + NT]
-  const int D4 = D >> 2;
-  const f32x4 *x4 = (const f32x4 *)x;
-  f32x4 q[NQ];
-#pragma unroll
-  for (int j = 0; j < NQ; j++) q[j] = x4[12 + j < D4 ? 12 + j : D4 - 1];
-#pragma unroll
-  for (int k = 0; k < NT; k++) tl[k] = q[(k + 1) >> 2][(k + 1) & 3];
 }
 
 // (the torch implementation's conv head, off the fused path: one wave per
@@ -157,11 +133,10 @@ struct PolicyArgs {
 __device__ __forceinline__ void philox_u8(unsigned long long seed, unsigned long long ctr0, float (&u)[8]) {
 #pragma unroll
   for (int b = 0; b < 2; b++) {
-    const unsigned long long ctr = ctr0 + (unsigned long long)b;
-    uint32_t o[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0x243F6A88u, 0x85A308D3u};
-    philox10(o, (uint32_t)seed, (uint32_t)(seed >> 32));
+    float ub[4];
+    philox_u4(seed, ctr0 + (unsigned long long)b, ub);
 #pragma unroll
-    for (int k = 0; k < 4; k++) u[4 * b + k] = (float)(o[k] >> 8) * 5.9604644775390625e-08f;
+    for (int k = 0; k < 4; k++) u[4 * b + k] = ub[k];
   }
 }
 
@@ -248,7 +223,7 @@ __device__ __forceinline__ f32x4v mfma32(const bf16x8 &a, const bf16x8 &b, f32x4
 // acc[rt][nt] += W (planes F: hi | mid | lo, each bf16x8 [nt][p][lane]) x X
 template <int NTO, int Q>
 __device__ __forceinline__ void mfma_layer3(const bf16x8 *__restrict__ F, const f32x4v (&xb)[4][Q],
-                                            f32x4v (&acc)[4][NTO], int lane, bf16x8 *split_save = nullptr) {
+                                            f32x4v (&acc)[4][NTO], int lane) {
   static_assert(Q % 2 == 0, "k in pairs of quads");
   constexpr int QP = Q / 2, PL = NTO * QP * WAVE;  // plane stride (bf16x8)
 #pragma unroll
@@ -256,22 +231,6 @@ __device__ __forceinline__ void mfma_layer3(const bf16x8 *__restrict__ F, const 
     bf16x8 b0[4], b1[4], b2[4];
 #pragma unroll
     for (int rt = 0; rt < 4; rt++) split3(xb[rt][2 * p], xb[rt][2 * p + 1], b0[rt], b1[rt], b2[rt]);
-#ifdef LNW_MLP_SPLIT_FENCE
-    // probe: every split term computed (materialised in its registers) before
-    // the first MFMA of the pair is issued: no vector instruction of this block
-    // co-executing with its MFMAs
-#pragma unroll
-    for (int rt = 0; rt < 4; rt++) asm volatile("" : "+v"(b0[rt]), "+v"(b1[rt]), "+v"(b2[rt]));
-    __builtin_amdgcn_sched_barrier(0);
-#endif
-    if (split_save && p == 0) {  // (diagnostics probe 16)
-#pragma unroll
-      for (int rt = 0; rt < 4; rt++) {
-        split_save[3 * rt] = b0[rt];
-        split_save[3 * rt + 1] = b1[rt];
-        split_save[3 * rt + 2] = b2[rt];
-      }
-    }
 #pragma unroll
     for (int nt = 0; nt < NTO; nt++) {
       const int i = (nt * QP + p) * WAVE + lane;
@@ -330,13 +289,9 @@ __host__ __device__ constexpr int mlp_bf16x8() {
 
 // fc1 / fc2 / fc3 and both heads of the wave's 64 rows on the matrix cores
 // (xb: fc1's B operand), then each row's head outputs brought to its own lane
-// (hh_save, xb_save: diagnostics probe 14 only)
 template <int Q1>
 __device__ __forceinline__ void mlp_heads(const PolicyArgs &pa, const bf16x8 *Fw, const float *xt, int lane,
-                                          int g, int m, float (&mean)[NOUT], float (&lsd)[NOUT],
-                                          f32x4v *hh_save = nullptr, f32x4v *xb_save = nullptr,
-                                          f32x4v *layers_save = nullptr, bf16x8 *split_save = nullptr,
-                                          f32x4v *pre_save = nullptr) {
+                                          int g, int m, float (&mean)[NOUT], float (&lsd)[NOUT]) {
   constexpr int KS = 16 * Q1 + 4;  // the tile's row stride (policy_act_kernel)
   const lnw_policy_args &a = pa.a;
   f32x4v xb[4][Q1];
@@ -344,60 +299,26 @@ __device__ __forceinline__ void mlp_heads(const PolicyArgs &pa, const bf16x8 *Fw
   for (int rt = 0; rt < 4; rt++)
 #pragma unroll
     for (int q = 0; q < Q1; q++) xb[rt][q] = *(const f32x4v *)(xt + (rt * 16 + m) * KS + 16 * q + 4 * g);
-  if (xb_save) {
-#pragma unroll
-    for (int rt = 0; rt < 4; rt++)
-#pragma unroll
-      for (int q = 0; q < Q1; q++) xb_save[rt * Q1 + q] = xb[rt][q];
-  }
   // weights: three bf16 planes per layer (mfma_layer3), layers in order
   // Fw: the three bf16 planes of every layer (global, or the block's LDS copy)
   constexpr int O2 = 3 * 4 * (Q1 / 2) * WAVE, O3 = O2 + 3 * 4 * 2 * WAVE, OH = O3 + 3 * 2 * 2 * WAVE;
   const float *bias = a.params + pa.off_b1;  // b1 [64] | b2 [64] | b3 [32]
   f32x4v h1[4][4];
   bias_init<4>(bias, h1, g);
-  mfma_layer3<4, Q1>(Fw, xb, h1, lane, split_save);
-  if (pre_save) {  // (diagnostics probe 16: fc1 before the activation)
-#pragma unroll
-    for (int rt = 0; rt < 4; rt++)
-#pragma unroll
-      for (int nt = 0; nt < 4; nt++) pre_save[rt * 4 + nt] = h1[rt][nt];
-  }
+  mfma_layer3<4, Q1>(Fw, xb, h1, lane);
   tanh_all<4>(h1);
-  if (layers_save) {  // probe 15: [layer 0..2][rt][nt] (h1, h2: 4 nt; h3: 2)
-#pragma unroll
-    for (int rt = 0; rt < 4; rt++)
-#pragma unroll
-      for (int nt = 0; nt < 4; nt++) layers_save[(0 * 4 + rt) * 4 + nt] = h1[rt][nt];
-  }
   f32x4v h2[4][4];
   bias_init<4>(bias + 64, h2, g);
   mfma_layer3<4, 4>(Fw + O2, h1, h2, lane);
   tanh_all<4>(h2);
-  if (layers_save) {
-#pragma unroll
-    for (int rt = 0; rt < 4; rt++)
-#pragma unroll
-      for (int nt = 0; nt < 4; nt++) layers_save[(1 * 4 + rt) * 4 + nt] = h2[rt][nt];
-  }
   f32x4v h3[4][2];
   bias_init<2>(bias + 128, h3, g);
   mfma_layer3<2, 4>(Fw + O3, h2, h3, lane);
   tanh_all<2>(h3);
-  if (layers_save) {
-#pragma unroll
-    for (int rt = 0; rt < 4; rt++)
-#pragma unroll
-      for (int nt = 0; nt < 2; nt++) layers_save[(2 * 4 + rt) * 4 + nt] = h3[rt][nt];
-  }
   f32x4v hh[4][1];
 #pragma unroll
   for (int rt = 0; rt < 4; rt++) hh[rt][0] = f32x4v{0.f, 0.f, 0.f, 0.f};
   mfma_layer3<1, 2>(Fw + OH, h3, hh, lane);
-  if (hh_save) {
-#pragma unroll
-    for (int rt = 0; rt < 4; rt++) hh_save[rt] = hh[rt][0];
-  }
   // head outputs of row 16 rt + m sit in lane m (normal head, n = v) and lane
   // 16 + m (log-std head, n = 4 + v) of tile rt: bring row `lane` to lane
   // `lane` (rt = g) for the per-row sampling below
@@ -419,55 +340,13 @@ __device__ __forceinline__ void mlp_heads(const PolicyArgs &pa, const bf16x8 *Fw
 // A wave's rows up to the fc1 tile: conv head + LayerNorm (one row per lane),
 // the observation copy for the rollout buffer, and the LayerNorm outputs into
 // the wave's fc1 input tile in LDS (xt) for mlp_heads.
-#if defined(LNW_PROBE_DISTURB) && (LNW_PROBE_DISTURB >= 12)
-// Diagnostics probe 12: the first head of every wave (all heads at once) saves
-// each stage of its rows here; the partner's second head, run while the other
-// wave of its SIMD runs its MLP, compares stage by stage (window loads, pooled
-// conv1 maps in LDS, conv head outputs, LayerNorm tail loads, LayerNorm
-// outputs) and counts rows that differ per stage and lane (lnw_probe_counts).
-constexpr int PROBE_ROWS = 131072, PROBE_W = 256;
-__device__ float probe_buf[(size_t)PROBE_ROWS * PROBE_W];
-constexpr int PROBE_STAGES = 10;
-#if LNW_PROBE_DISTURB >= 15
-__device__ f32x4v probe_layers[(size_t)131072 * 48];  // probe 15: every lane's h1 / h2 / h3 from its phase run
-#endif
-#if LNW_PROBE_DISTURB == 16
-__device__ bf16x8 probe_split[(size_t)131072 * 12];  // probe 16: fc1's bf16 split terms (k-pair 0), per rt
-__device__ f32x4v probe_pre[(size_t)131072 * 16];    // probe 16: fc1 before tanh
-#endif
-__device__ unsigned probe_cnt[PROBE_STAGES * 64];
-template <int N>
-__device__ __forceinline__ void probe_stage(int cmp, int stage, long long row, int off, const float (&v)[N],
-                                            int lane) {
-  if (row >= PROBE_ROWS) return;
-  float *b = probe_buf + (size_t)row * PROBE_W + off;
-  if (!cmp) {
-#pragma unroll
-    for (int k = 0; k < N; k++) b[k] = v[k];
-    return;
-  }
-  bool bad = false;
-#pragma unroll
-  for (int k = 0; k < N; k++) bad = bad || __float_as_uint(b[k]) != __float_as_uint(v[k]);
-  if (bad) atomicAdd(&probe_cnt[stage * 64 + lane], 1u);
-}
-#if LNW_PROBE_DISTURB == 12
-#define PROBE_STAGE(st, off, v) probe_stage(probe_cmp, st, r0 + (threadIdx.x & ~(WAVE - 1)) + lane, off, v, lane)
-#else
-#define PROBE_STAGE(st, off, v) ((void)0)
-#endif
-#else
-#define PROBE_STAGE(st, off, v) ((void)0)
-#endif
-
 template <int NI>
 __device__ __forceinline__ void head_to_tile(const PolicyArgs &pa, const float *P, float *warea, int lane,
                                              bool valid, long long e, int i, long long istride, long long r0,
-                                             long long rows, int probe_cmp = 0) {
+                                             long long rows) {
   constexpr int KS = NI + 4;
   const lnw_policy_args &a = pa.a;
   const int n = a.n, D = a.D, n_in = pa.n_in;
-  (void)probe_cmp;
   // ---- conv head + LayerNorm, one row per lane -------------------------------
   // The row's window and LayerNorm tail are loaded once, every load issued
   // together, into registers (the tail's loads were one dependent round trip
@@ -480,20 +359,7 @@ __device__ __forceinline__ void head_to_tile(const PolicyArgs &pa, const float *
       float win[WIN];
 #pragma unroll
       for (int k = 0; k < WIN; k++) win[k] = x[k];
-#ifdef LNW_PROBE_NOCONV  // timing probes only (tools/policy_probe.py): no conv head
-      for (int k = 0; k < 12; k++) h[k] = win[k];
-#else
-      PROBE_STAGE(0, 0, win);
       conv_head_win(P, win, warea + lane, WAVE, a.bn_running != 0, h);
-#if defined(LNW_PROBE_DISTURB) && LNW_PROBE_DISTURB == 12
-      {
-        float pm[45];
-        for (int k = 0; k < 45; k++) pm[k] = warea[lane + k * WAVE];
-        PROBE_STAGE(1, 49, pm);
-      }
-#endif
-      PROBE_STAGE(2, 94, h);
-#endif
     }
     // the tail after the head (its registers are the head's), one batch of loads;
     // the row's address again from an opaque copy of the row index, so no 64-bit
@@ -504,14 +370,8 @@ __device__ __forceinline__ void head_to_tile(const PolicyArgs &pa, const float *
     asm volatile("" : "+v"(r_t));
     const int e_t = r_t / n, i_t = r_t - e_t * n;
     const float *xt = a.obs + (long long)e_t * istride + (long long)i_t * D;
-#ifdef LNW_POLICY_SCALAR_TAIL  // (probe builds: the per-value loads, A/B)
-    load_tail(xt, D, tl);
-#else
-    load_tail_q(xt, D, tl);
-#endif
-    PROBE_STAGE(3, 106, tl);
+    load_tail_q(xt, D >> 2, tl);
     layer_norm_tail<NI>(P, tl, n_in, h, u);
-    PROBE_STAGE(4, 170, u);
   } else {
 #pragma unroll
     for (int k = 0; k < NI; k++) u[k] = 0.f;
@@ -524,9 +384,6 @@ __device__ __forceinline__ void head_to_tile(const PolicyArgs &pa, const float *
   // (in place: lnw_observe_ex wrote the rows into the rollout buffer itself;
   // only the rows of envs whose episode ended are zeroed)
   const bool in_place = a.obs_out == a.obs && a.obs_env_stride == istride;
-#if defined(LNW_PROBE_DISTURB) && LNW_PROBE_DISTURB == 12
-  if (probe_cmp) return;
-#endif
   if (a.obs_out && (!in_place || a.live)) {
     const int D4 = D >> 2;
     const long long rw = r0 + (threadIdx.x & ~(WAVE - 1));
@@ -550,113 +407,7 @@ __device__ __forceinline__ void head_to_tile(const PolicyArgs &pa, const float *
   for (int k4 = 0; k4 < NI / 4; k4++)
     *(f32x4v *)(xt + lane * KS + 4 * k4) = f32x4v{u[4 * k4], u[4 * k4 + 1], u[4 * k4 + 2], u[4 * k4 + 3]};
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#if defined(LNW_PROBE_DISTURB) && LNW_PROBE_DISTURB >= 13
-  // Diagnostics probe 13 (the head/MLP overlap schedule of probe 10): every head
-  // saves the row it wrote; the second head (probe_cmp, beside the SIMD
-  // partner's MLP) reads its tile row back at once and counts lanes whose
-  // bytes differ from what it wrote (stage 0); head_and_mlp checks the tile
-  // again just before this wave's own MLP (stage 1)
-  {
-    const long long grow = r0 + (threadIdx.x & ~(WAVE - 1)) + lane;
-    if (grow < PROBE_ROWS) {
-      float *b = probe_buf + (size_t)grow * PROBE_W;
-#pragma unroll
-      for (int k = 0; k < NI; k++) b[k] = u[k];
-    }
-    if (probe_cmp) {
-      bool bad = false;
-#pragma unroll
-      for (int k4 = 0; k4 < NI / 4; k4++) {
-        f32x4v v = *(const f32x4v *)(xt + lane * KS + 4 * k4);
-        asm volatile("" : "+v"(v));
-#pragma unroll
-        for (int j = 0; j < 4; j++) bad = bad || __float_as_uint(v[j]) != __float_as_uint(u[4 * k4 + j]);
-      }
-      if (bad) atomicAdd(&probe_cnt[0 * 64 + lane], 1u);
-    }
-  }
-#endif
 }
-
-#ifdef LNW_PROBE_DISTURB
-// Diagnostics probes only: what the other wave of a SIMD does while a wave
-// runs its MLP (1 VALU FMA chains, 2 LDS reads of its own tile, 3 global
-// loads, 4 s_sleep, 5 MFMA chains on registers, 6 LDS writes past its tile,
-// 7 global stores to its rows' log-prob outputs (rewritten after), 8 v_exp /
-// v_log / v_rcp / v_sqrt chains, 9 integer hashing; 10, in head_and_mlp: its
-// own head again, rewriting the same tile; 11 its tile rows read and written
-// back unchanged; 12 its head again, compared stage by stage, probe_stage);
-// nothing it computes is kept.
-template <int MODE, int KS>
-__device__ __forceinline__ void disturb(const PolicyArgs &pa, float *warea, int lane, long long e, int i) {
-  float acc0 = (float)lane, acc1 = 1.f, acc2 = 2.f, acc3 = 3.f;
-  if (MODE == 1) {
-    for (int it = 0; it < 2000; it++) {
-      acc0 = fmaf(acc0, 1.0001f, 0.5f); acc1 = fmaf(acc1, 0.9999f, 0.25f);
-      acc2 = fmaf(acc2, 1.0002f, 0.125f); acc3 = fmaf(acc3, 0.9998f, 0.0625f);
-    }
-  } else if (MODE == 2) {
-    for (int it = 0; it < 600; it++) {
-      const f32x4v v = *(const f32x4v *)(warea + ((lane + it) & 63) * KS + 4 * (it & 3));
-      acc0 += v[0]; acc1 += v[1]; acc2 += v[2]; acc3 += v[3];
-    }
-  } else if (MODE == 3) {
-    const float *q = pa.a.params + pa.off_w1;
-    for (int it = 0; it < 300; it++) {
-      const f32x4v v = *(const f32x4v *)(q + 4 * ((lane + 64 * it) & 4095));
-      acc0 += v[0]; acc1 += v[1]; acc2 += v[2]; acc3 += v[3];
-    }
-  } else if (MODE == 4) {
-    for (int it = 0; it < 100; it++) __builtin_amdgcn_s_sleep(8);
-  } else if (MODE == 6) {
-    for (int it = 0; it < 600; it++) {
-      acc0 = fmaf(acc0, 1.0001f, 0.5f);
-      warea[64 * KS + lane + 64 * (it % ((45 * 64 - 64 * KS) / 64 > 0 ? (45 * 64 - 64 * KS) / 64 : 1))] = acc0;
-    }
-  } else if (MODE == 7) {
-    float *o = pa.a.logp_out ? pa.a.logp_out + e * pa.a.act_env_stride + 4 * i : nullptr;
-    for (int it = 0; it < 300 && o; it++) {
-      acc0 = fmaf(acc0, 1.0001f, 0.5f);
-      o[it & 3] = acc0;
-    }
-  } else if (MODE == 8) {
-    for (int it = 0; it < 500; it++) {
-      acc0 = __builtin_amdgcn_exp2f(acc0 * 1e-3f); acc1 = __builtin_amdgcn_logf(acc1 + 1.f);
-      acc2 = __builtin_amdgcn_rcpf(acc2 + 1.f); acc3 = __builtin_amdgcn_sqrtf(acc3 + 1.f);
-    }
-  } else if (MODE == 11) {  // its own tile row read and written back, unchanged
-    float *row = warea + lane * KS;
-    for (int it = 0; it < 60; it++) {
-      f32x4v v[KS / 4 - 1];
-#pragma unroll
-      for (int k4 = 0; k4 < KS / 4 - 1; k4++) {
-        v[k4] = *(const f32x4v *)(row + 4 * k4);
-        asm volatile("" : "+v"(v[k4]));  // (not a load-store pair the compiler may drop)
-      }
-#pragma unroll
-      for (int k4 = 0; k4 < KS / 4 - 1; k4++) *(f32x4v *)(row + 4 * k4) = v[k4];
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    }
-  } else if (MODE == 9) {
-    unsigned h0 = (unsigned)lane, h1 = 7u;
-    for (int it = 0; it < 1000; it++) {
-      h0 = __umulhi(h0 ^ 0x9E3779B9u, 0xD2511F53u) + h1;
-      h1 = h1 * 0xCD9E8D57u + h0;
-    }
-    acc0 = (float)h0; acc1 = (float)h1;
-  } else {
-    bf16x8 w;
-#pragma unroll
-    for (int j = 0; j < 8; j++) w[j] = (__bf16)(0.001f * (float)(lane + j));
-    f32x4v c0 = {0.f, 0.f, 0.f, 0.f}, c1 = c0, c2 = c0, c3 = c0;
-    for (int it = 0; it < 400; it++) {
-      c0 = mfma32(w, w, c0); c1 = mfma32(w, w, c1); c2 = mfma32(w, w, c2); c3 = mfma32(w, w, c3);
-    }
-    acc0 = c0[0] + c1[1] + c2[2] + c3[3];
-  }
-  asm volatile("" ::"v"(acc0), "v"(acc1), "v"(acc2), "v"(acc3));
-}
-#endif
 
 // The phases of a block. PA_THREADS = 512 (one block per CU, two waves per
 // SIMD): every wave runs its head, a barrier, then every wave its MLP. A wave's
@@ -665,183 +416,19 @@ __device__ __forceinline__ void disturb(const PolicyArgs &pa, float *warea, int 
 // 48-63 of the head's wave ("The policy kernel's nondeterminism");
 // heads beside heads and MLPs beside MLPs are exact. (One block per CU: the
 // block's LDS is larger than half the CU's, so no other block's head shares a
-// SIMD with these MLPs.) The diagnostics probes keep round 5's schedule, the
-// waves of each SIMD taking their MLPs one at a time, to run their partner
-// workloads beside each MLP.
+// SIMD with these MLPs.)
 template <int NI>
 __device__ __forceinline__ void head_and_mlp(const PolicyArgs &pa, const float *P, const bf16x8 *Fw, float *warea, int lane, int g,
                                              int m, bool valid, long long e, int i, long long istride, long long r0,
                                              long long rows, float (&mean)[NOUT], float (&lsd)[NOUT]) {
   constexpr int Q1 = NI / 16;
   head_to_tile<NI>(pa, P, warea, lane, valid, e, i, istride, r0, rows);
-#ifndef LNW_PROBE_DISTURB
-#ifndef LNW_POLICY_OVERLAP  // (probe builds: each wave's MLP right after its own head)
-  if constexpr (PA_THREADS > WAVE) __syncthreads();  // every head done before any MLP
-#endif
+  __syncthreads();  // every head done before any MLP
   mlp_heads<Q1>(pa, Fw, warea, lane, g, m, mean, lsd);
-#else
-  constexpr int NWB = PA_THREADS / WAVE;
-  __shared__ int simd_of[NWB];
-  const int wv = (int)(threadIdx.x / WAVE);
-  const int simd = (int)((__builtin_amdgcn_s_getreg((31 << 11) | 4) >> 4) & 3);  // hwreg(HW_ID).SIMD_ID
-  if (lane == 0) simd_of[wv] = simd;
-  __syncthreads();
-  int rank = 0, nph = 1;  // this wave's turn on its SIMD; turns needed by the busiest SIMD
-#pragma unroll
-  for (int w2 = 0; w2 < NWB; w2++) {
-    int r2 = 0;
-#pragma unroll
-    for (int w3 = 0; w3 < w2; w3++) r2 += simd_of[w3] == simd_of[w2] ? 1 : 0;
-    nph = r2 + 1 > nph ? r2 + 1 : nph;
-    rank = w2 == wv ? r2 : rank;
-  }
-#if LNW_PROBE_DISTURB >= 14
-  f32x4v hh1[4];
-#endif
-  for (int ph = 0; ph < nph; ph++) {
-#if LNW_PROBE_DISTURB == 13 || LNW_PROBE_DISTURB == 14  // this wave's tile row against what its head wrote, just before its MLP
-    if (ph == rank) {
-      constexpr int KS = NI + 4;
-      const long long grow = r0 + (threadIdx.x & ~(WAVE - 1)) + lane;
-      bool bad = false;
-      if (grow < PROBE_ROWS) {
-        const float *b = probe_buf + (size_t)grow * PROBE_W;
-#pragma unroll
-        for (int k4 = 0; k4 < NI / 4; k4++) {
-          f32x4v v = *(const f32x4v *)(warea + lane * KS + 4 * k4);
-          asm volatile("" : "+v"(v));
-#pragma unroll
-          for (int j = 0; j < 4; j++) bad = bad || __float_as_uint(v[j]) != __float_as_uint(b[4 * k4 + j]);
-        }
-      }
-      if (bad) atomicAdd(&probe_cnt[1 * 64 + lane], 1u);
-    }
-#endif
-#if LNW_PROBE_DISTURB == 16
-    if (ph == rank) {
-      const size_t t = (size_t)blockIdx.x * PA_THREADS + threadIdx.x;
-      mlp_heads<Q1>(pa, Fw, warea, lane, g, m, mean, lsd, hh1, nullptr, probe_layers + t * 48,
-                    probe_split + t * 12, probe_pre + t * 16);
-    }
-#elif LNW_PROBE_DISTURB == 15
-    if (ph == rank) {
-      f32x4v *ls = probe_layers + ((size_t)blockIdx.x * PA_THREADS + threadIdx.x) * 48;
-      mlp_heads<Q1>(pa, Fw, warea, lane, g, m, mean, lsd, hh1, nullptr, ls);
-    }
-#elif LNW_PROBE_DISTURB == 14
-    if (ph == rank) {
-      // the MLP's fc1 operands as it loaded them from the tile, against the saved
-      // rows (stage 2); its head outputs (hh) kept for the rerun below
-      f32x4v xs[4 * Q1];
-      mlp_heads<Q1>(pa, Fw, warea, lane, g, m, mean, lsd, hh1, xs);
-      bool bad = false;
-#pragma unroll
-      for (int rt = 0; rt < 4; rt++) {
-        const long long grow = r0 + (threadIdx.x & ~(WAVE - 1)) + rt * 16 + m;
-        if (grow >= PROBE_ROWS) continue;
-        const float *b = probe_buf + (size_t)grow * PROBE_W;
-#pragma unroll
-        for (int q = 0; q < Q1; q++)
-#pragma unroll
-          for (int j = 0; j < 4; j++)
-            bad = bad || __float_as_uint(xs[rt * Q1 + q][j]) != __float_as_uint(b[16 * q + 4 * g + j]);
-      }
-      if (bad) atomicAdd(&probe_cnt[2 * 64 + lane], 1u);
-    }
-#else
-    if (ph == rank) mlp_heads<Q1>(pa, Fw, warea, lane, g, m, mean, lsd);
-#endif
-#if LNW_PROBE_DISTURB == 10 || LNW_PROBE_DISTURB >= 13  // the partner redoes its head (same tile)
-    else head_to_tile<NI>(pa, P, warea, lane, valid, e, i, istride, r0, rows, LNW_PROBE_DISTURB >= 13);
-#elif LNW_PROBE_DISTURB == 12  // ... comparing every stage
-    else head_to_tile<NI>(pa, P, warea, lane, valid, e, i, istride, r0, rows, 1);
-#else  // the partner's work (tools/build_probes.sh)
-    else disturb<LNW_PROBE_DISTURB, NI + 4>(pa, warea, lane, e, i);
-#endif
-    __syncthreads();
-  }
-#if LNW_PROBE_DISTURB == 16
-  {  // stages: 0/1 split terms (rt 0-2 / rt 3), 2/3 fc1 before tanh, 4/5 h1 after tanh
-    float m2[NOUT], l2[NOUT];
-    f32x4v hh2[4], l2s[48], pre2[16];
-    bf16x8 sp2[12];
-    mlp_heads<Q1>(pa, Fw, warea, lane, g, m, m2, l2, hh2, nullptr, l2s, sp2, pre2);
-    const size_t t = (size_t)blockIdx.x * PA_THREADS + threadIdx.x;
-    const bf16x8 *sp = probe_split + t * 12;
-    const f32x4v *pr = probe_pre + t * 16, *ls = probe_layers + t * 48;
-    bool bad[3][2] = {{false, false}, {false, false}, {false, false}};
-#pragma unroll
-    for (int rt = 0; rt < 4; rt++) {
-#pragma unroll
-      for (int k = 0; k < 3; k++)
-#pragma unroll
-        for (int j = 0; j < 8; j++)
-          bad[0][rt == 3] = bad[0][rt == 3] || __builtin_bit_cast(unsigned short, sp[3 * rt + k][j]) !=
-                                                   __builtin_bit_cast(unsigned short, sp2[3 * rt + k][j]);
-#pragma unroll
-      for (int nt = 0; nt < 4; nt++)
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-          bad[1][rt == 3] = bad[1][rt == 3] || __float_as_uint(pr[rt * 4 + nt][j]) != __float_as_uint(pre2[rt * 4 + nt][j]);
-          bad[2][rt == 3] = bad[2][rt == 3] || __float_as_uint(ls[rt * 4 + nt][j]) != __float_as_uint(l2s[rt * 4 + nt][j]);
-        }
-    }
-#pragma unroll
-    for (int L = 0; L < 3; L++)
-#pragma unroll
-      for (int u = 0; u < 2; u++)
-        if (bad[L][u]) atomicAdd(&probe_cnt[(2 * L + u) * 64 + lane], 1u);
-  }
-#elif LNW_PROBE_DISTURB == 15
-  {  // per layer (h1, h2, h3, heads) and row tile: stage 2 L + (rt == 3), L = layer
-    float m2[NOUT], l2[NOUT];
-    f32x4v hh2[4], l2s[48];
-    mlp_heads<Q1>(pa, Fw, warea, lane, g, m, m2, l2, hh2, nullptr, l2s);
-    const f32x4v *ls = probe_layers + ((size_t)blockIdx.x * PA_THREADS + threadIdx.x) * 48;
-    bool bad[4][2] = {{false, false}, {false, false}, {false, false}, {false, false}};
-#pragma unroll
-    for (int L = 0; L < 3; L++)
-#pragma unroll
-      for (int rt = 0; rt < 4; rt++)
-#pragma unroll
-        for (int nt = 0; nt < (L == 2 ? 2 : 4); nt++)
-#pragma unroll
-          for (int j = 0; j < 4; j++)
-            bad[L][rt == 3] = bad[L][rt == 3] ||
-                              __float_as_uint(ls[(L * 4 + rt) * 4 + nt][j]) != __float_as_uint(l2s[(L * 4 + rt) * 4 + nt][j]);
-#pragma unroll
-    for (int rt = 0; rt < 4; rt++)
-#pragma unroll
-      for (int j = 0; j < 4; j++) bad[3][rt == 3] = bad[3][rt == 3] || __float_as_uint(hh2[rt][j]) != __float_as_uint(hh1[rt][j]);
-#pragma unroll
-    for (int L = 0; L < 4; L++)
-#pragma unroll
-      for (int t = 0; t < 2; t++)
-        if (bad[L][t]) atomicAdd(&probe_cnt[(2 * L + t) * 64 + lane], 1u);
-  }
-#elif LNW_PROBE_DISTURB == 14
-  {  // stage 3: the final per-row outputs, stage 4: the head outputs before the gather
-    float m2[NOUT], l2[NOUT];
-    f32x4v hh2[4];
-    mlp_heads<Q1>(pa, Fw, warea, lane, g, m, m2, l2, hh2);
-    bool bo = false, bh = false;
-#pragma unroll
-    for (int v = 0; v < NOUT; v++)
-      bo = bo || __float_as_uint(m2[v]) != __float_as_uint(mean[v]) || __float_as_uint(l2[v]) != __float_as_uint(lsd[v]);
-#pragma unroll
-    for (int rt = 0; rt < 4; rt++)
-#pragma unroll
-      for (int j = 0; j < 4; j++) bh = bh || __float_as_uint(hh2[rt][j]) != __float_as_uint(hh1[rt][j]);
-    if (bo) atomicAdd(&probe_cnt[3 * 64 + lane], 1u);
-    if (bh) atomicAdd(&probe_cnt[4 * 64 + lane], 1u);
-  }
-#endif
-#endif
 }
 
 template <int NI>
-__global__ __launch_bounds__(PA_THREADS, 512 / PA_THREADS) void policy_act_kernel(PolicyArgs pa) {
-  constexpr int Q1 = NI / 16;        // fc1 k-quads (n_in zero-padded to NI)
+__global__ __launch_bounds__(PA_THREADS, 1) void policy_act_kernel(PolicyArgs pa) {
   constexpr int KS = NI + 4;         // row stride of the wave's fc1 input tile (16-B aligned)
   const lnw_policy_args &a = pa.a;
   const int n_in = pa.n_in;
@@ -900,15 +487,7 @@ __global__ __launch_bounds__(PA_THREADS, 512 / PA_THREADS) void policy_act_kerne
   }
   // ---- head, fc1 tile and MLP (phases: head_and_mlp) --------------------------
   float mean[NOUT], lsd[NOUT];
-#ifdef LNW_PROBE_NOMLP  // timing / diagnostics probes only: no MLP (the lane's own fc1 tile row)
-  head_to_tile<NI>(pa, P, warea, lane, valid, e, i, istride, r0, rows);
-  for (int v = 0; v < NOUT; v++) {
-    mean[v] = warea[lane * KS + 12 + v];
-    lsd[v] = 0.f;
-  }
-#else
   head_and_mlp<NI>(pa, P, Fw, warea, lane, g, m, valid, e, i, istride, r0, rows, mean, lsd);
-#endif
   if (!valid) return;
   // the row's env and ship again, from an opaque copy of the row index: so
   // they are recomputed here instead of living across the head (where the
@@ -1141,7 +720,7 @@ extern "C" {
 int lnw_actor_features(const float *params_dev, int32_t obs_dim, const float *obs_dev, int64_t B,
                        int32_t bn_running, float *out_dev, void *stream) {
   if (!params_dev || !obs_dev || !out_dev || B < 0) return LNW_EINVAL;
-  if (obs_dim < WIN || obs_dim - WIN + 12 > MAX_IN) return LNW_EUNSUPPORTED;
+  if (!obs_width_ok(obs_dim, false)) return LNW_EUNSUPPORTED;  // (per-value tail loads: any width)
   if (B == 0) return 0;
   const long long blocks = (B + CH_THREADS - 1) / CH_THREADS;  // one row per thread
   if (B >= (1ll << 31) - CH_THREADS) return LNW_EUNSUPPORTED;  // (32-bit rows)
@@ -1167,7 +746,7 @@ int lnw_policy_act(const lnw_policy_args *args, void *stream) {
   const lnw_policy_args &a = *args;
   if (!a.obs || !a.params || !a.alive || a.n <= 0 || a.E < 0 || a.A <= 0 || a.own0 < 0 || a.own0 + a.n > a.A)
     return LNW_EINVAL;
-  if (a.D < WIN || a.D - WIN + 12 > MAX_IN || (a.D & 3)) return LNW_EUNSUPPORTED;
+  if (!obs_width_ok(a.D, true)) return LNW_EUNSUPPORTED;
   if (a.forced && !a.forced_act) return LNW_EINVAL;
   if (!a.forced && a.T <= 0) return LNW_EINVAL;
   if (a.script && (!a.full || a.script_own0 < 0 || a.script_own0 + a.script_cnt > a.A)) return LNW_EINVAL;
@@ -1195,9 +774,6 @@ int lnw_policy_act(const lnw_policy_args *args, void *stream) {
   const int npar4 = (CONV_PARAMS + 2 * pa.n_in + 3) & ~3;
   size_t lds = (size_t)(npar4 + (PA_THREADS / WAVE) * (pa.n_in <= 32 ? 45 : MAX_IN + 4) * WAVE) * sizeof(float);
   if (pa.n_in <= 32) lds += (size_t)mlp_bf16x8<32>() * 16;  // the MLP weights' LDS copy
-#ifdef LNW_PROBE_ONEBLOCK  // probe builds: one block per CU
-  if (lds < 84 * 1024) lds = 84 * 1024;
-#endif
   // One block per CU: head_and_mlp's schedule (every head, a barrier, every MLP)
   // keeps a head from running beside an MLP only within the block, so no other
   // block may share the CU. The block asks for more than half of the CU's LDS,
@@ -1218,15 +794,6 @@ int lnw_policy_act(const lnw_policy_args *args, void *stream) {
     policy_act_kernel<MAX_IN><<<blocks, PA_THREADS, lds, (hipStream_t)stream>>>(pa);
   return hipGetLastError() == hipSuccess ? 0 : LNW_EDEVICE;
 }
-
-#if defined(LNW_PROBE_DISTURB) && (LNW_PROBE_DISTURB >= 12)
-// probe 12's / 13's counters [stage][lane] since the last call (then zeroed)
-int lnw_probe_counts(unsigned *host) {
-  if (hipMemcpyFromSymbol(host, HIP_SYMBOL(probe_cnt), sizeof(probe_cnt)) != hipSuccess) return LNW_EDEVICE;
-  static const unsigned zero[PROBE_STAGES * 64] = {};
-  return hipMemcpyToSymbol(HIP_SYMBOL(probe_cnt), zero, sizeof(zero)) == hipSuccess ? 0 : LNW_EDEVICE;
-}
-#endif
 
 // Packed critic: see rollout_post_kernel (BatchedCritic.packed()).
 int lnw_rollout_post(const lnw_rollout_post_args *args, void *stream) {

@@ -132,6 +132,18 @@ __device__ inline void philox10(uint32_t c[4], uint32_t k0, uint32_t k1) {
   }
 }
 
+// One Philox block as four float uniforms in [0, 1): the block at 64-bit counter
+// ctr under the key seed, the top 24 bits of each word times 2^-24. This is what
+// lnw_fill_uniform_f32 writes (four values per counter) and what the policy's and
+// the Q-network's keyed draws read, so shards of the envs draw what one fill
+// over all of them holds.
+__device__ inline void philox_u4(unsigned long long seed, unsigned long long ctr, float (&u)[4]) {
+  uint32_t o[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0x243F6A88u, 0x85A308D3u};
+  philox10(o, (uint32_t)seed, (uint32_t)(seed >> 32));
+#pragma unroll
+  for (int k = 0; k < 4; k++) u[k] = (float)(o[k] >> 8) * 5.9604644775390625e-08f;
+}
+
 __device__ inline double u53(uint32_t a, uint32_t b) {
   return ((double)(a >> 5) * 67108864.0 + (double)(b >> 6)) / 9007199254740992.0;
 }

@@ -3881,12 +3881,11 @@ __global__ void fill_uniform_kernel(float *out, long long n, unsigned long long 
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   long long base = i * 4;
   if (base >= n) return;
-  unsigned long long ctr = (offset >> 2) + (unsigned long long)i;
-  uint32_t o[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0x243F6A88u, 0x85A308D3u};
-  philox10(o, (uint32_t)seed, (uint32_t)(seed >> 32));
+  float u[4];
+  philox_u4(seed, (offset >> 2) + (unsigned long long)i, u);
 #pragma unroll
   for (int k = 0; k < 4; k++)
-    if (base + k < n) out[base + k] = (float)(o[k] >> 8) * 5.9604644775390625e-08f;
+    if (base + k < n) out[base + k] = u[k];
 }
 
 // ===========================================================================

@@ -44,13 +44,13 @@ namespace {
 
 using namespace lnw;
 
-#include "lnw_convhead.inc"
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int MAX_IN = 64;       // n_in = D - 49 + 12 bound (as lnw_qnet_act)
+#include "lnw_convhead.inc"
+#include "lnw_qhead.inc"
+
 constexpr int QL_THREADS = 128;  // rows per workgroup
 constexpr int QL_WAVES = QL_THREADS / WAVE;
-constexpr int Q_OUT = 57;
-constexpr int BIAS_PAD = 60;
 // LDS copy of the conv head's parameters: the packed 578, with the statistics in
 // use in the M / V slots, then 1 / sqrt(var + eps) of the 5 + 8 channels
 constexpr int I1 = CONV_PARAMS, I2 = CONV_PARAMS + 5, CONV_LDS = 592;
@@ -67,8 +67,6 @@ enum { RED_FWD = 0, RED_HEAD = 1, RED_CONV2 = 2, RED_CONV1 = 3 };
 constexpr int WS_H = 0, WS_DS = 12, WS_GY2 = 15, WS_GY1 = 23, WS_OIDX = 68, WS_POS2 = 71, WS_POS1 = 72, WS_FIELDS = 77;
 
 extern __shared__ float ql_lds[];
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct Ws {
   double *stat1;  // [2 nets][sum 5, sumsq 5]
@@ -152,16 +150,6 @@ __device__ __forceinline__ void stage_conv(float *P, const float *params, const 
   __syncthreads();
 }
 
-// head weights zero-padded to NI columns, and biases
-template <int NI>
-__device__ __forceinline__ void stage_heads(float *Wl, float *bl, const float *params, int n_in) {
-  for (int i = threadIdx.x; i < Q_OUT * NI; i += QL_THREADS) {
-    const int o = i / NI, k = i - o * NI;
-    Wl[i] = k < n_in ? params[CONV_PARAMS + o * n_in + k] : 0.f;
-  }
-  for (int i = threadIdx.x; i < Q_OUT; i += QL_THREADS) bl[i] = params[CONV_PARAMS + Q_OUT * n_in + i];
-}
-
 __device__ __forceinline__ void load_win(const float *row, float (&win)[WIN]) {
   const f32x4 *r4 = (const f32x4 *)row;
 #pragma unroll
@@ -175,27 +163,7 @@ __device__ __forceinline__ void load_win(const float *row, float (&win)[WIN]) {
   win[48] = row[48];
 }
 
-// ---- forward pieces -------------------------------------------------------------
-// conv1 (1 -> 5, 3x3, pad 1), channel c, as conv_head_win
-__device__ __forceinline__ void conv1_ch(const float *P, const float (&win)[WIN], int c, float (&v)[49]) {
-#pragma clang fp contract(fast)
-  const float *w = P + C1W + c * 9;
-#pragma unroll
-  for (int i = 0; i < 7; i++)
-#pragma unroll
-    for (int j = 0; j < 7; j++) {
-      float s = P[C1B + c];
-#pragma unroll
-      for (int ki = 0; ki < 3; ki++)
-#pragma unroll
-        for (int kj = 0; kj < 3; kj++) {
-          const int ii = i + ki - 1, jj = j + kj - 1;
-          if (ii >= 0 && ii < 7 && jj >= 0 && jj < 7) s += w[ki * 3 + kj] * win[ii * 7 + jj];
-        }
-      v[i * 7 + j] = s;
-    }
-}
-
+// ---- forward pieces (conv1_ch, conv2_raw: lnw_convhead.inc) -----------------------
 // first maximum of a window's four values in row-major order (strict >)
 __device__ __forceinline__ float first_max4(float a, float b, float c, float d, int &sel) {
   float best = a;
@@ -227,57 +195,11 @@ __device__ __forceinline__ void fwd_p1(const float *P, const float (&win)[WIN], 
   }
 }
 
-// conv2 (5 -> 8, 3x3, pad 1) of the pooled maps in pc, output maps c0 .. c0 + 3
-__device__ __forceinline__ void conv2_raw(const float *P, const float *pc, int c0, float (&v2)[4][9]) {
-#pragma clang fp contract(fast)
-#pragma unroll
-  for (int co = 0; co < 4; co++)
-#pragma unroll
-    for (int p = 0; p < 9; p++) v2[co][p] = P[C2B + c0 + co];
-#pragma unroll 1
-  for (int ci = 0; ci < 5; ci++) {
-    float pin[9];
-#pragma unroll
-    for (int k = 0; k < 9; k++) pin[k] = pc[(ci * 9 + k) * QL_THREADS];
-#pragma unroll
-    for (int co = 0; co < 4; co++) {
-      const float *w = P + C2W + ((c0 + co) * 5 + ci) * 9;
-#pragma unroll
-      for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++)
-#pragma unroll
-          for (int ki = 0; ki < 3; ki++)
-#pragma unroll
-            for (int kj = 0; kj < 3; kj++) {
-              const int ii = i + ki - 1, jj = j + kj - 1;
-              if (ii >= 0 && ii < 3 && jj >= 0 && jj < 3) v2[co][i * 3 + j] += w[ki * 3 + kj] * pin[ii * 3 + jj];
-            }
-    }
-  }
-}
-
 // x[12 ..] = obs[49 .. D - 1], zeros past n_in
 template <int NI>
 __device__ __forceinline__ void load_tail(const float *row, int n_in, float (&x)[NI]) {
 #pragma unroll
   for (int k = 12; k < NI; k++) x[k] = k < n_in ? row[37 + k] : 0.f;
-}
-
-// W[o] . x + b[o] from the zero-padded LDS copy (four chains, as q_head of lnw_qnet.hip)
-template <int NI>
-__device__ __forceinline__ float head_dot(const float *Wl, const float *bl, const float (&x)[NI], int o) {
-  const f32x4 *w = (const f32x4 *)(Wl + o * NI);
-  float s0 = bl[o], s1 = 0.f, s2 = 0.f, s3 = 0.f;
-#pragma unroll
-  for (int k4 = 0; k4 < NI / 4; k4++) {
-    const f32x4 wv = w[k4];
-    s0 = fmaf(wv[0], x[4 * k4], s0);
-    s1 = fmaf(wv[1], x[4 * k4 + 1], s1);
-    s2 = fmaf(wv[2], x[4 * k4 + 2], s2);
-    s3 = fmaf(wv[3], x[4 * k4 + 3], s3);
-  }
-  return (s0 + s1) + (s2 + s3);
 }
 
 template <int NI>
@@ -350,7 +272,7 @@ __global__ __launch_bounds__(QL_THREADS) void ql_moments2_kernel(lnw_qlearn_args
 #pragma unroll 1
     for (int c0 = 0; c0 < 8; c0 += 4) {
       float v2[4][9];
-      conv2_raw(P, pc, c0, v2);
+      conv2_raw(P, pc, QL_THREADS, c0, v2);
 #pragma unroll
       for (int co = 0; co < 4; co++) {
         double s = 0.0, q = 0.0;
@@ -394,8 +316,8 @@ __global__ __launch_bounds__(QL_THREADS) void ql_forward_kernel(lnw_qlearn_args 
   const double n1 = 49.0 * (double)a.rows, n2 = 9.0 * (double)a.rows;
   stage_conv(Pp, a.policy_params, w.stat1, n1, w.stat2, n2, a.policy_bn_running == 0);
   stage_conv(Pt, a.target_params, w.stat1 + 10, n1, w.stat2 + 16, n2, true);
-  stage_heads<NI>(Wp, bp, a.policy_params, n_in);
-  stage_heads<NI>(Wt, bt, a.target_params, n_in);
+  stage_heads<NI>(Wp, bp, a.policy_params, n_in, QL_THREADS);
+  stage_heads<NI>(Wt, bt, a.target_params, n_in, QL_THREADS);
   __syncthreads();
   const long long r = (long long)blockIdx.x * QL_THREADS + threadIdx.x;
   const bool valid = r < a.rows;
@@ -440,7 +362,7 @@ __global__ __launch_bounds__(QL_THREADS) void ql_forward_kernel(lnw_qlearn_args 
 #pragma unroll
     for (int c0 = 0; c0 < 8; c0 += 4) {
       float v2[4][9];
-      conv2_raw(Pp, pc, c0, v2);
+      conv2_raw(Pp, pc, QL_THREADS, c0, v2);
 #pragma unroll
       for (int co = 0; co < 4; co++) {
         const int c = c0 + co;
@@ -584,7 +506,7 @@ __global__ __launch_bounds__(QL_THREADS) void ql_conv2grad_kernel(lnw_qlearn_arg
 #pragma unroll 1
     for (int c0 = 0; c0 < 8; c0 += 4) {
       float dz[4][9];
-      conv2_raw(P, pA, c0, dz);
+      conv2_raw(P, pA, QL_THREADS, c0, dz);
       // BN2 backward: dz = g inv (dy - mean(dy) - xh mean(dy xh)); dy is gy2 at the pool's position
 #pragma unroll
       for (int co = 0; co < 4; co++) {
@@ -835,8 +757,6 @@ int slab_width(int n_in) {
   return ((head > SLAB_MIN ? head : SLAB_MIN) + 3) & ~3;
 }
 
-bool dims_ok(int D) { return D >= WIN && D - WIN + 12 <= MAX_IN && !(D & 3); }
-
 // The double a float argument was before the ABI narrowed it: the shortest
 // decimal that rounds to the float (0.9f -> 0.9, 1e-4f -> 1e-4), else the float.
 double as_decimal(float x) {
@@ -853,7 +773,7 @@ double as_decimal(float x) {
 extern "C" {
 
 int64_t lnw_qlearn_workspace_bytes(int64_t rows, int32_t D) {
-  if (rows < 1 || rows + QL_THREADS >= (1ll << 31) || !dims_ok(D)) return 0;
+  if (rows < 1 || rows + QL_THREADS >= (1ll << 31) || !obs_width_ok(D, true)) return 0;
   const int64_t nblk = (rows + QL_THREADS - 1) / QL_THREADS;
   return 512 + nblk * 32 * 8 + nblk * slab_width(D - WIN + 12) * 4 + (int64_t)WS_FIELDS * nblk * QL_THREADS * 4;
 }
@@ -867,7 +787,7 @@ int lnw_qnet_grad(const lnw_qlearn_args *args, void *stream) {
   if (a.rows < 1 || a.action_stride < 3) return LNW_EINVAL;
   // 16-B aligned rows for the vector loads
   if (((uintptr_t)a.state & 15) || ((uintptr_t)a.next_state & 15) || ((uintptr_t)a.workspace & 15)) return LNW_EINVAL;
-  if (!dims_ok(a.D)) return LNW_EUNSUPPORTED;
+  if (!obs_width_ok(a.D, true)) return LNW_EUNSUPPORTED;
   if (a.rows + QL_THREADS >= (1ll << 31)) return LNW_EUNSUPPORTED;
   if (a.workspace_bytes < lnw_qlearn_workspace_bytes(a.rows, a.D)) return LNW_EINVAL;
   const int n_in = a.D - WIN + 12;

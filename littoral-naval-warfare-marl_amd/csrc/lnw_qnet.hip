@@ -33,27 +33,21 @@ namespace {
 
 using namespace lnw;
 
-#include "lnw_convhead.inc"
-
-constexpr int MAX_IN = 64;   // n_in = D - 49 + 12 bound (as lnw_actor_features)
-constexpr int QN_THREADS = 256;
-constexpr int Q_RAD = 2, Q_ATK = 5, Q_MOV = 50, Q_OUT = Q_RAD + Q_ATK + Q_MOV;  // 57
-constexpr int CONV_PAD = (CONV_PARAMS + 3) & ~3;  // 16-B aligned weight rows behind the conv block
-constexpr int BIAS_PAD = (Q_OUT + 3) & ~3;
-
-extern __shared__ float qnet_lds[];
-
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
-// the four keyed uniforms of a global row (fill_uniform_kernel's block)
+#include "lnw_convhead.inc"
+#include "lnw_qhead.inc"
+
+constexpr int QN_THREADS = 256;
+constexpr int CONV_PAD = (CONV_PARAMS + 3) & ~3;  // 16-B aligned weight rows behind the conv block
+
+extern __shared__ float qnet_lds[];
+
+// the four keyed uniforms of a global row (lnw_fill_uniform_f32's block)
 __device__ __forceinline__ void keyed_u4(unsigned long long seed, unsigned long long slot, long long grow,
                                          float (&u)[4]) {
-  const unsigned long long ctr = (slot << 38) + (unsigned long long)grow;
-  uint32_t o[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0x243F6A88u, 0x85A308D3u};
-  philox10(o, (uint32_t)seed, (uint32_t)(seed >> 32));
-#pragma unroll
-  for (int k = 0; k < 4; k++) u[k] = (float)(o[k] >> 8) * 5.9604644775390625e-08f;
+  philox_u4(seed, (slot << 38) + (unsigned long long)grow, u);
 }
 
 // One head: outputs o0 .. o0 + cnt - 1 of relu(W x + b), streamed; returns the
@@ -66,17 +60,7 @@ __device__ __forceinline__ int q_head(const float *Wl, const float *bl, const fl
 #pragma unroll 1
   for (int j = 0; j < cnt; j++) {
     const int o = o0 + j;
-    const f32x4 *w = (const f32x4 *)(Wl + o * NI);
-    float s0 = bl[o], s1 = 0.f, s2 = 0.f, s3 = 0.f;  // four chains: k = 0, 1, 2, 3 mod 4
-#pragma unroll
-    for (int k4 = 0; k4 < NI / 4; k4++) {
-      const f32x4 wv = w[k4];
-      s0 = fmaf(wv[0], x[4 * k4], s0);
-      s1 = fmaf(wv[1], x[4 * k4 + 1], s1);
-      s2 = fmaf(wv[2], x[4 * k4 + 2], s2);
-      s3 = fmaf(wv[3], x[4 * k4 + 3], s3);
-    }
-    const float s = (s0 + s1) + (s2 + s3);
+    const float s = head_dot<NI>(Wl, bl, x, o);
     const float q = s < 0.f ? 0.f : s;  // relu: a NaN stays a NaN (torch.relu)
     if (qo) qo[o] = q;
     const bool better = j == 0 || q > best || (q != q && best == best);
@@ -94,11 +78,7 @@ __global__ __launch_bounds__(QN_THREADS, 2) void qnet_act_kernel(lnw_qnet_args a
   // pooled conv1 maps: per wave [45][64], one column per lane (as features_kernel)
   float *pool1 = bl + BIAS_PAD + (threadIdx.x / WAVE) * 45 * WAVE + (threadIdx.x & (WAVE - 1));
   for (int i = threadIdx.x; i < CONV_PARAMS; i += blockDim.x) P[i] = a.params[i];
-  for (int i = threadIdx.x; i < Q_OUT * NI; i += blockDim.x) {
-    const int o = i / NI, k = i - o * NI;
-    Wl[i] = k < n_in ? a.params[CONV_PARAMS + o * n_in + k] : 0.f;
-  }
-  for (int i = threadIdx.x; i < Q_OUT; i += blockDim.x) bl[i] = a.params[CONV_PARAMS + Q_OUT * n_in + i];
+  stage_heads<NI>(Wl, bl, a.params, n_in, blockDim.x);
   __syncthreads();
   const int n = a.n, D = a.D;
   const long long rows = a.E * n;
@@ -120,17 +100,13 @@ __global__ __launch_bounds__(QN_THREADS, 2) void qnet_act_kernel(lnw_qnet_args a
   asm volatile("" : "+v"(r_o));
   const int e = r_o / n, i = r_o - e * n;
   {
-    // x[12 ..] = obs[49 .. D - 1]: the float4 quads from obs[48] on (16-B aligned
-    // rows of D % 4 == 0 floats, checked on the host; quad indices clamped into
-    // the row), zeros past n_in
-    constexpr int NQ = (NI - 12 + 1 + 3) / 4;
+    // x[12 ..] = obs[49 .. D - 1] (16-B aligned rows of D % 4 == 0 floats, checked
+    // on the host), zeros past n_in
+    float tl[NI - 12];
     const int D4 = D >> 2;
-    const f32x4 *x4 = (const f32x4 *)(a.obs + (long long)e * istride + (long long)i * D);
-    f32x4 q[NQ];
+    load_tail_q(a.obs + (long long)e * istride + (long long)i * D, D4, tl);
 #pragma unroll
-    for (int j = 0; j < NQ; j++) q[j] = x4[12 + j < D4 ? 12 + j : D4 - 1];
-#pragma unroll
-    for (int k = 12; k < NI; k++) x[k] = k < n_in ? q[(k - 11) >> 2][(k - 11) & 3] : 0.f;
+    for (int k = 12; k < NI; k++) x[k] = k < n_in ? tl[k - 12] : 0.f;
   }
   float *qo = a.q_out ? a.q_out + (long long)r_o * Q_OUT : nullptr;
   int act[3];
@@ -202,7 +178,7 @@ int lnw_qnet_act(const lnw_qnet_args *args, void *stream) {
   if ((net && ((uintptr_t)a.obs & 15)) || (a.full && ((uintptr_t)a.full & 15)) ||
       (a.act_out && (((uintptr_t)a.act_out & 15) || (a.act_env_stride & 3) || a.act_env_stride < (int64_t)a.n * 4)))
     return LNW_EINVAL;
-  if (a.D < WIN || a.D - WIN + 12 > MAX_IN || (net && (a.D & 3))) return LNW_EUNSUPPORTED;
+  if (!obs_width_ok(a.D, net)) return LNW_EUNSUPPORTED;  // (no row is read without a network)
   const long long rows = a.E * a.n;
   if (rows + QN_THREADS >= (1ll << 31)) return LNW_EUNSUPPORTED;  // (32-bit row indices)
   if (a.E == 0) return 0;

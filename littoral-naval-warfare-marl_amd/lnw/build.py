@@ -22,7 +22,7 @@ SOURCES = [os.path.join(CSRC, "lnw_kernels.hip"), os.path.join(CSRC, "lnw_actor.
            os.path.join(CSRC, "lnw_qnet.hip"), os.path.join(CSRC, "lnw_qlearn.hip")]
 DEPS = SOURCES + [os.path.join(CSRC, "lnw_device.h"), os.path.join(CSRC, "lnw_quiet.inc"),
                   os.path.join(CSRC, "lnw_group.inc"), os.path.join(CSRC, "lnw_convhead.inc"),
-                  os.path.join(INCLUDE, "lnw.h")]
+                  os.path.join(CSRC, "lnw_qhead.inc"), os.path.join(INCLUDE, "lnw.h")]
 
 
 def hipcc():

@@ -3,8 +3,8 @@
 strided in place like the rollout's direct path) -- are the outputs
 bit-identical from call to call?
 usage: python tools/policy_determinism.py [E] [reps] [variants,...]
-POLICY_LIB=path: an lnw_actor.hip-only build (tools/probe). Differing rows are
-reported with their 64-row waves."""
+POLICY_LIB=path: another build of lnw_actor.hip alone (an A/B build under
+tools/probe). Differing rows are reported with their 64-row waves."""
 import ctypes as C
 import os
 import sys
@@ -18,7 +18,7 @@ def main():
     from lnw import _abi
     from lnw.rollout import BatchedActor
     path = os.environ.get("POLICY_LIB")
-    if path:  # an lnw_actor.hip-only build (tools/probe)
+    if path:  # another build of lnw_actor.hip alone
         L = C.CDLL(path)
         L.lnw_policy_act.argtypes = [C.POINTER(_abi.PolicyArgs), C.c_void_p]
         print("lib", path, flush=True)
@@ -114,33 +114,6 @@ def main():
                         print(var, "rep", k, name, int((x != y).sum()), "differ, max |d|",
                               float((x - y).abs().max()), "rows", sorted(set(rr.tolist()))[:6],
                               "waves", sorted(set((rr // 64).tolist()))[:6], flush=True)
-        if hasattr(L, "lnw_probe_counts"):  # probe 12: rows whose second head differed, per stage
-            cnt = (C.c_uint * 640)()
-            L.lnw_probe_counts(cnt)
-            names = (["fc1 bf16 split terms, row tiles 0-2", "fc1 bf16 split terms, row tile 3",
-                      "fc1 before tanh, row tiles 0-2", "fc1 before tanh, row tile 3",
-                      "h1 after tanh, row tiles 0-2", "h1 after tanh, row tile 3", "-", "-", "-", "-"]
-                     if "disturb16" in (path or "") else
-                     [f"layer {lay} ({'heads' if lay == 'h4' else 'tanh'}) in row tiles {t} vs the rerun"
-                      for lay in ("h1", "h2", "h3", "h4") for t in ("0-2", "3")]
-                     if "disturb15" in (path or "") else
-                     ["tile read back after the second head's write (beside the partner's MLP)",
-                      "tile row just before the wave's own MLP",
-                      "fc1 operands as the MLP loaded them from the tile",
-                      "per-row outputs vs a rerun of the MLP (MLPs beside MLPs)",
-                      "head outputs before the lane gather vs the rerun"]
-                     if ("disturb13" in (path or "") or "disturb14" in (path or "")) else
-                     ["window loads", "pooled conv1 maps (LDS)", "conv head out", "LayerNorm tail loads",
-                      "LayerNorm out"])
-            for st, name in enumerate(names):
-                if name == "-":
-                    continue
-                c = list(cnt[st * 64:(st + 1) * 64])
-                if sum(c):
-                    ln = [l for l in range(64) if c[l]]
-                    print(var, "probe stage", name, ":", sum(c), "rows, lanes", ln[0], "..", ln[-1], flush=True)
-                else:
-                    print(var, "probe stage", name, ": 0 rows", flush=True)
         print(var, "mismatching (rep, output) pairs:", nd, "of", len(ref) * (reps - 1),
               "waves involved:", len(waves), sorted(waves)[:10],
               "lanes:", (min(lanes), max(lanes)) if lanes else None, flush=True)

@@ -3,7 +3,8 @@
 lnw_policy_act and lnw_rollout_post over config 5's 32 768 4v4 envs (131 072
 actor rows) on random observation rows, HIP-event timed on the launch stream.
 usage: python tools/policy_probe.py [lib.so ...]   (default: the in-tree
-liblnw.so; tools/probe/*.so are lnw_actor.hip builds with LNW_PROBE_* defines)."""
+liblnw.so; any other library that exports the two entry points works, e.g. an
+earlier build of lnw_actor.hip alone kept under tools/probe for an A/B)."""
 import ctypes as C
 import os
 import sys
