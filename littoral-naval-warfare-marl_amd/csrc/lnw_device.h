@@ -56,8 +56,30 @@ struct KParams {
   int no_obs;         // lnw_step without observation outputs (both pointers NULL)
   long long obs_stride[2];  // lnw_observe_ex: floats between envs' rows per side (0: packed)
   int dbg_skip;       // diagnostics only (LNW_DEBUG_SKIP): bit0 obs, bit1 phase S, bit2 phase M, bit7 get_obs in S, bit8 reward, bit9 no quiet path, bit10 no window reads in quiet emission, bit11 no phase-S LOS prefetch, bit12 device atan2 instead of the bearing table, bit13 4-ship phase-S rows stored row by row instead of line-aligned, bit15 the group kernel's fire loop entry by entry
-  int qdirect;        // (last: the tail padding; the fields above keep their kernarg offsets) quiet workgroups stage whole 64-row side blocks (qbig) and wave 1 writes every row itself, in slabs of 64 / nb envs (step_qdirect)
+  int qdirect;        // quiet workgroups stage whole 64-row side blocks (qbig) and wave 1 writes every row itself, in slabs of 64 / nb envs (step_qdirect)
 };
+
+// Cold block: the part of the device state that only the loud (phase S / O),
+// in-kernel reset, tape-RNG and analytics paths read. One device-resident copy
+// per distinct set of values and handle (lnw_kernels.hip: cold_commit); the
+// kernels get a pointer to it instead of the values, which keeps them out of
+// the step kernels' argument segment.
+struct KCold {
+  lnw_analytics ana;  // analytics side channels (null pointers: off)
+  const double *tape;
+  const long long *tape_off;
+  // spawn spec (auto-reset)
+  const int32_t *sp_types;   // [A]
+  const int32_t *sp_pos;     // [A][2]
+  const int32_t *sp_randls;  // [A]
+  const int32_t *sp_pos_env; // [E][A][2] or null
+  double *bear_val;    // [nmax*nmax][E] EW bearing scratch
+  uint8_t *bear_ship;  // [nmax*nmax][E]
+  unsigned long long *ctr;   // lnw_set_counters work counters (null: off)
+};
+static_assert(sizeof(KCold) == sizeof(lnw_analytics) + 9 * 8 && sizeof(lnw_analytics) == 72,
+              "KCold must have no implicit padding (blocks are compared bytewise)");
+typedef const KCold *ColdPtr;
 
 // Device state (SoA, agent-major [field][agent][env] so a wave of envs reads
 // one agent's field with coalesced accesses).
@@ -76,26 +98,16 @@ struct KState {
   int32_t *envi;       // [8][E]
   unsigned long long *rng;  // [E]
   uint32_t *err;       // [E]
-  double *bear_val;    // [nmax*nmax][E] EW bearing scratch
-  uint8_t *bear_ship;  // [nmax*nmax][E]
   const double *atan_deg;  // [LOS_W][LOS_W] degrees(atan2(dy, dx)), host libm (EW bearings)
   const uint8_t *grid;     // [G][G]
   const float *gridf;      // [G][G] grid/255 as float32
   const float *winf;       // [3][G*G][52] Combatant 7x7 | LandingShip 5x5 | medium Combatant 5x5 observation windows
   float *dummy;            // [WAVE * 4] sink for masked-out stores (keeps store counts static)
   unsigned long long *prof;  // diagnostics (LNW_PROF): [n_wg][16] phase timestamps, else null
-  lnw_analytics ana;         // analytics side channels (null pointers: off)
-  unsigned long long *ctr;   // lnw_set_counters work counters (null: off)
+  ColdPtr cold;              // the handle's cold block (analytics, work counters, tape RNG, spawn spec, bearing scratch: KCold)
   const uint32_t *mask2;   // [G][W16] 2 bits per cell: bit0 > move_thr, bit1 > ew_thr
   const uint32_t *mvtab;   // [3][G*G][3] move tables: Combatant speed 3 | LandingShip | medium Combatant speed 2
   const uint32_t *lostab;  // [G*G][486]
-  const double *tape;
-  const long long *tape_off;
-  // spawn spec (auto-reset)
-  const int32_t *sp_types;   // [A]
-  const int32_t *sp_pos;     // [A][2]
-  const int32_t *sp_randls;  // [A]
-  const int32_t *sp_pos_env; // [E][A][2] or null
   int nmax;
 };
 

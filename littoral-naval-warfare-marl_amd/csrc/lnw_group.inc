@@ -482,7 +482,7 @@ __device__ __forceinline__ void get_obs_group(Ctx &X, int me, int sub, const GSi
   }
   GPROF_ADD(X, 5, tq);
   const uint32_t fixm = group_ballot(n >= 2, gsh);  // opponents with a fix
-  if (S.ctr && n >= 2) X.pooled += (unsigned)n;     // work counter: this column's pooled bearings
+  if (S.cold->ctr && n >= 2) X.pooled += (unsigned)n;     // work counter: this column's pooled bearings
   // pooled: the group's fix bearings spread over its lanes by rank (ceil(k / GL)
   // slopes per lane, two at a time) into ms, read back by the opponent lanes
   if (fixm && !(P.dbg_skip & 16384)) {
@@ -552,9 +552,9 @@ __device__ __forceinline__ void get_obs_group(Ctx &X, int me, int sub, const GSi
           err |= LNW_ERRF_NAN_ROUND;
         } else {
           const double rx = rint(mx), ry = rint(my);
-          if (S.ana.ew_log) {  // combatant.py:146-150: (observer position, rounded fix)
+          if (S.cold->ana.ew_log) {  // combatant.py:146-150: (observer position, rounded fix)
             const int ax = (int)fmin(fmax(rx, -32768.0), 32767.0), ay = (int)fmin(fmax(ry, -32768.0), 32767.0);
-            ana_record(S.ana.ew_log, S.ana.ew_count, S.ana.ew_cap, (uint32_t)(P.env_base + env),
+            ana_record(S.cold->ana.ew_log, S.cold->ana.ew_count, S.cold->ana.ew_cap, (uint32_t)(P.env_base + env),
                        (uint32_t)X.step | (uint32_t)side << 16, COLW(c.pos_cur, me),
                        (uint32_t)(uint16_t)ax | (uint32_t)(uint16_t)ay << 16);
           }
@@ -852,7 +852,7 @@ __global__ __launch_bounds__(GEPW * GL) void step_group_kernel(
           // entries side by side unless an analytics map or the engagement log
           // wants fire_dev's per-hit records in list order (LNW_DEBUG_SKIP bit 15:
           // entry by entry always)
-          const bool par = !S.ana.heatmap && !S.ana.coldmap && !S.ana.launch && !S.ana.eng_log &&
+          const bool par = !S.cold->ana.heatmap && !S.cold->ana.coldmap && !S.cold->ana.launch && !S.cold->ana.eng_log &&
                            !(P.dbg_skip & 32768);
           for (int q0 = 0; q0 < tn; q0 += GL) {
             const int q = q0 + sub;
@@ -898,7 +898,7 @@ __global__ __launch_bounds__(GEPW * GL) void step_group_kernel(
     }
     env_tail(P, S, c, slot, env, nb, A, N, ev, hits, nbp, nrp, bsx, bsy, rsx, rsy, X.rng, rew_b,
              rew_r, done_out, cog_out);
-    if (S.ctr && X.pooled) atomicAdd(&S.ctr[3], (unsigned long long)X.pooled);
+    if (S.cold->ctr && X.pooled) atomicAdd(&S.cold->ctr[3], (unsigned long long)X.pooled);
     GPROF_ADD(X, 2, t0);
     GPROF_FLUSH(X);
   }

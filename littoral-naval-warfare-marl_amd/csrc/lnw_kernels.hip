@@ -326,7 +326,7 @@ __device__ inline bool check_path_h(const KParams &P, const KState &S, int type,
   }
   MaskBlocked mb{S.mask2, P.W16};
   bool sb = mb(sx, sy);
-  if (S.ctr) atomicAdd(&S.ctr[2], 1ull);  // A* searches run (work counter)
+  if (S.cold->ctr) atomicAdd(&S.cold->ctr[2], 1ull);  // A* searches run (work counter)
   return check_path_dev(mb, sb, P.G, type, sx, sy, tx, ty, open, ost);
 }
 
@@ -340,11 +340,11 @@ __device__ inline bool can_move_to_h(const KParams &P, const KState &S, int x, i
 // visited)
 __device__ inline uint32_t los_march_c(const KState &S, const uint32_t *mask, int W16, int x1,
                                        int y1, int x2, int y2) {
-  if (!S.ctr) return los_march<true>(mask, W16, x1, y1, x2, y2);
+  if (!S.cold->ctr) return los_march<true>(mask, W16, x1, y1, x2, y2);
   int n = 0;
   const uint32_t r = los_march<true>(mask, W16, x1, y1, x2, y2, &n);
-  atomicAdd(&S.ctr[0], 1ull);
-  atomicAdd(&S.ctr[1], (unsigned long long)n);
+  atomicAdd(&S.cold->ctr[0], 1ull);
+  atomicAdd(&S.cold->ctr[1], (unsigned long long)n);
   return r;
 }
 
@@ -458,8 +458,8 @@ __device__ inline void pair_after_los(Ctx &X, int i, int jj, int xi, int yi, int
     int k = COLB(c.bcnt, jj);
     if (k == 0) { COLB(c.border, acc.norder) = (uint8_t)jj; acc.norder++; }
     size_t slot = (size_t)(jj * S.nmax + k) * X.E + X.env;
-    S.bear_val[slot] = bearing;
-    S.bear_ship[slot] = (uint8_t)i;
+    S.cold->bear_val[slot] = bearing;
+    S.cold->bear_ship[slot] = (uint8_t)i;
     COLB(c.bcnt, jj) = (uint8_t)(k + 1);
   }
 }
@@ -489,8 +489,8 @@ __device__ inline void pair_after_los_m(Ctx &X, int i, int jj, int opp0, int nop
     int k = COLB(c.bcnt, jj);
     if (k == 0) { COLB(c.border, acc.norder) = (uint8_t)jj; acc.norder++; }
     size_t slot = (size_t)(jj * S.nmax + k) * X.E + X.env;
-    S.bear_val[slot] = bearing;
-    S.bear_ship[slot] = (uint8_t)i;
+    S.cold->bear_val[slot] = bearing;
+    S.cold->bear_ship[slot] = (uint8_t)i;
     COLB(c.bcnt, jj) = (uint8_t)(k + 1);
   }
 }
@@ -555,8 +555,8 @@ __device__ inline bool fix_mean_loop(Ctx &X, int jj, int n, double &mx, double &
   const int m = n - 1;
   FixAcc f;
   for (int k = 0; k < m; k++) {
-    uint8_t s1 = S.bear_ship[slot(k)], s2 = S.bear_ship[slot(k + 1)];
-    double b1 = S.bear_val[slot(k)], b2 = S.bear_val[slot(k + 1)];
+    uint8_t s1 = S.cold->bear_ship[slot(k)], s2 = S.cold->bear_ship[slot(k + 1)];
+    double b1 = S.cold->bear_val[slot(k)], b2 = S.cold->bear_val[slot(k + 1)];
     uint32_t p1 = COLW(c.pos_cur, s1), p2 = COLW(c.pos_cur, s2);
     double m1 = tan_fd(b1 * DEG2RAD);
     double m2 = tan_fd(b2 * DEG2RAD);
@@ -583,7 +583,7 @@ __device__ inline bool fix_mean_batched(Ctx &X, int jj, int n, double &mx, doubl
   for (int k = 0; k < BMAX; k++) {
     bv[k] = 0.0;
     bs[k] = 0;
-    if (k < n) { bv[k] = S.bear_val[slot(k)]; bs[k] = S.bear_ship[slot(k)]; }
+    if (k < n) { bv[k] = S.cold->bear_val[slot(k)]; bs[k] = S.cold->bear_ship[slot(k)]; }
   }
   double tv[BMAX], px[BMAX], py[BMAX];
 #pragma unroll
@@ -648,9 +648,9 @@ __device__ inline void finish_obs(Ctx &X, int me, int opp0, int opp1, const ObsA
     if (!ok) { X.rng.err |= LNW_ERRF_ZERODIV; continue; }
     if (!isfinite(mx) || !isfinite(my)) { X.rng.err |= LNW_ERRF_NAN_ROUND; continue; }
     double rx = rint(mx), ry = rint(my);
-    if (S.ana.ew_log) {  // combatant.py:146-150: (observer position, rounded fix)
+    if (S.cold->ana.ew_log) {  // combatant.py:146-150: (observer position, rounded fix)
       const int fx = (int)fmin(fmax(rx, -32768.0), 32767.0), fy = (int)fmin(fmax(ry, -32768.0), 32767.0);
-      ana_record(S.ana.ew_log, S.ana.ew_count, S.ana.ew_cap, (uint32_t)(P.env_base + env),
+      ana_record(S.cold->ana.ew_log, S.cold->ana.ew_count, S.cold->ana.ew_cap, (uint32_t)(P.env_base + env),
                  (uint32_t)X.step | (uint32_t)(me >= P.nb) << 16, COLW(c.pos_cur, me),
                  (uint32_t)(uint16_t)fx | (uint32_t)(uint16_t)fy << 16);
     }
@@ -704,9 +704,9 @@ __device__ __forceinline__ void march_pairs_ref(Ctx &X, int me) {
       const uint32_t pj = COLW(c.pos_cur, j);
       int n = 0;
       acc += los_march<false>(X.mask, P.W16, pos_x(pi), pos_y(pi), pos_x(pj), pos_y(pj), &n);
-      if (X.S.ctr) {
-        atomicAdd(&X.S.ctr[0], 1ull);
-        atomicAdd(&X.S.ctr[1], (unsigned long long)n);
+      if (X.S.cold->ctr) {
+        atomicAdd(&X.S.cold->ctr[0], 1ull);
+        atomicAdd(&X.S.cold->ctr[1], (unsigned long long)n);
       }
     }
   }
@@ -913,9 +913,9 @@ __device__ inline void finish_obs_t(Ctx &X, int me, int own0, int opp0, int obs_
     const double mx = sumx / (double)(cnt - 1), my = sumy / (double)(cnt - 1);
     if (!isfinite(mx) || !isfinite(my)) { X.rng.err |= LNW_ERRF_NAN_ROUND; return; }
     const double rx = rint(mx), ry = rint(my);
-    if (S.ana.ew_log) {  // combatant.py:146-150: (observer position, rounded fix)
+    if (S.cold->ana.ew_log) {  // combatant.py:146-150: (observer position, rounded fix)
       const int fx = (int)fmin(fmax(rx, -32768.0), 32767.0), fy = (int)fmin(fmax(ry, -32768.0), 32767.0);
-      ana_record(S.ana.ew_log, S.ana.ew_count, S.ana.ew_cap, (uint32_t)(P.env_base + env),
+      ana_record(S.cold->ana.ew_log, S.cold->ana.ew_count, S.cold->ana.ew_cap, (uint32_t)(P.env_base + env),
                  (uint32_t)X.step | (uint32_t)(me >= P.nb) << 16, COLW(c.pos_cur, me),
                  (uint32_t)(uint16_t)fx | (uint32_t)(uint16_t)fy << 16);
     }
@@ -987,7 +987,7 @@ __device__ inline void finish_obs_t(Ctx &X, int me, int own0, int opp0, int obs_
                                              __builtin_amdgcn_mbcnt_lo((uint32_t)bb, 0u)) << b;
       total += __popcll(bb) << b;
     }
-    if (S.ctr && rank == 0) atomicAdd(&S.ctr[3], (unsigned long long)total);  // work counter
+    if (S.cold->ctr && rank == 0) atomicAdd(&S.cold->ctr[3], (unsigned long long)total);  // work counter
     // in the observed-list / bearing-order columns (unused by the contact
     // variant's walk; >= 396 B per opponent slot, this needs 192 + 256 per
     // opponent): rank -> lane, rank -> first bearing number, and the fix table
@@ -1030,9 +1030,9 @@ __device__ inline void finish_obs_t(Ctx &X, int me, int own0, int opp0, int obs_
     auto draw = [&](int s, unsigned long long d) -> double {
       const int es = env - lane + s;
       if (tape) {
-        if (!S.tape_off) return 0.0;
-        const long long p = S.tape_off[es] + (long long)d;
-        return p < S.tape_off[es + 1] ? S.tape[p] : 0.0;
+        if (!S.cold->tape_off) return 0.0;
+        const long long p = S.cold->tape_off[es] + (long long)d;
+        return p < S.cold->tape_off[es + 1] ? S.cold->tape[p] : 0.0;
       }
       const unsigned long long gid = (unsigned long long)(P.env_base + es);
       return X.rng.gauss_philox(d, (uint32_t)gid, (uint32_t)(gid >> 32));
@@ -1048,9 +1048,9 @@ __device__ inline void finish_obs_t(Ctx &X, int me, int own0, int opp0, int obs_
           w = 1u << 18;
         } else {
           const double rx = rint(mx), ry = rint(my);
-          if (S.ana.ew_log) {  // combatant.py:146-150: (observer position, rounded fix)
+          if (S.cold->ana.ew_log) {  // combatant.py:146-150: (observer position, rounded fix)
             const int fx = (int)fmin(fmax(rx, -32768.0), 32767.0), fy = (int)fmin(fmax(ry, -32768.0), 32767.0);
-            ana_record(S.ana.ew_log, S.ana.ew_count, S.ana.ew_cap, (uint32_t)(P.env_base + env - lane + s),
+            ana_record(S.cold->ana.ew_log, S.cold->ana.ew_count, S.cold->ana.ew_cap, (uint32_t)(P.env_base + env - lane + s),
                        (uint32_t)stp | (uint32_t)(me >= P.nb) << 16, c.pos_cur[me * PAD + s],
                        (uint32_t)(uint16_t)fx | (uint32_t)(uint16_t)fy << 16);
           }
@@ -1118,7 +1118,7 @@ __device__ inline void finish_obs_t(Ctx &X, int me, int own0, int opp0, int obs_
         ZB = !fB && (ZA || zB);
       }
       int stA = 0, stB = 0;
-      if (S.ana.ew_log) {
+      if (S.cold->ana.ew_log) {
         stA = __shfl(X.step, sA);
         stB = __shfl(X.step, sB);
       }
@@ -1708,13 +1708,13 @@ __device__ inline bool fire_dev(Ctx &X, int a, int tx, int ty, double salvo, int
     const KState &S = X.S;
     if (missile) {  // combatant.py:642-652: maps of the trained side, launch sites of both
       if (side == (P.side_blue ? 0 : 1)) {
-        ana_map(S.ana.heatmap, pa);
-        ana_map(S.ana.coldmap, pt);
+        ana_map(S.cold->ana.heatmap, pa);
+        ana_map(S.cold->ana.coldmap, pt);
       }
-      if (S.ana.launch) ana_map(S.ana.launch + side * 10000, pa);
+      if (S.cold->ana.launch) ana_map(S.cold->ana.launch + side * 10000, pa);
     }
-    if (S.ana.eng_log)  // combatant.py:656-657
-      ana_record(S.ana.eng_log, S.ana.eng_count, S.ana.eng_cap, (uint32_t)(P.env_base + X.env),
+    if (S.cold->ana.eng_log)  // combatant.py:656-657
+      ana_record(S.cold->ana.eng_log, S.cold->ana.eng_count, S.cold->ana.eng_cap, (uint32_t)(P.env_base + X.env),
                  (uint32_t)X.step | (uint32_t)side << 16 | (uint32_t)n << 24, pa, pt);
   }
   if (hit) {
@@ -1830,14 +1830,14 @@ __device__ __forceinline__ void reset_env_dev(const KParams &P, const KState &S,
   unsigned long long box_ctr = ((unsigned long long)(uint32_t)S.envi[7 * E + env]) << 32;
   for (int a = 0; a < P.A; a++) {
     size_t ai = (size_t)a * E + env;
-    int t = S.sp_types[a];
+    int t = S.cold->sp_types[a];
     int x, y;
-    if (S.sp_pos_env) {
-      x = S.sp_pos_env[((size_t)env * P.A + a) * 2];
-      y = S.sp_pos_env[((size_t)env * P.A + a) * 2 + 1];
+    if (S.cold->sp_pos_env) {
+      x = S.cold->sp_pos_env[((size_t)env * P.A + a) * 2];
+      y = S.cold->sp_pos_env[((size_t)env * P.A + a) * 2 + 1];
     } else {
-      x = S.sp_pos[2 * a];
-      y = S.sp_pos[2 * a + 1];
+      x = S.cold->sp_pos[2 * a];
+      y = S.cold->sp_pos[2 * a + 1];
     }
     if (box) {
       for (int tries = 0; tries < 64; tries++) {
@@ -1853,7 +1853,7 @@ __device__ __forceinline__ void reset_env_dev(const KParams &P, const KState &S,
         if (!(cell_bits(S.mask2, P.W16, bx, by) & 1u)) { x = bx; y = by; break; }
       }
     }
-    if (S.sp_randls[a]) {
+    if (S.cold->sp_randls[a]) {
       x = rng.randint(98, 99);
       y = rng.randint(48, 56);
     }
@@ -1890,12 +1890,15 @@ __device__ inline Rng make_rng(const KParams &P, const KState &S, int env) {
   r.g1 = (uint32_t)(gid >> 32);
   r.ctr = S.rng[env];
   r.err = 0;
-  r.tape = S.tape;
-  if (P.rng_mode == 1 && S.tape_off) {
-    r.tape_lo = S.tape_off[env];
-    r.tape_hi = S.tape_off[env + 1];
-  } else {
-    r.tape_lo = r.tape_hi = 0;
+  // (the tape is read in tape mode only: Philox launches never touch the cold block here)
+  r.tape = nullptr;
+  r.tape_lo = r.tape_hi = 0;
+  if (P.rng_mode == 1) {
+    r.tape = S.cold->tape;
+    if (S.cold->tape_off) {
+      r.tape_lo = S.cold->tape_off[env];
+      r.tape_hi = S.cold->tape_off[env + 1];
+    }
   }
   return r;
 }
@@ -2967,7 +2970,7 @@ extern __shared__ __attribute__((aligned(16))) char lds_dyn[];
 template <int NB, int NR, bool CW, bool REFW, int UN, bool PS, bool SL>
 __device__ __forceinline__ void step_body(
     const KParams &P, KState S, void *actions, const uint8_t *row_kind, float *obs_b, float *obs_r,
-    float *rew_b, float *rew_r, int32_t *done_out, float *cog_out) {
+    float *rew_b, float *rew_r, int32_t *done_out, float *cog_out, unsigned long long t_entry = 0) {
   static_assert(UN == 1 || (NB > 0 && EPW == WAVE && !REFW), "units need the two-wave templated kernel");
   const int unit = UN > 1 ? (int)(threadIdx.x / (2 * WAVE)) : 0;
   const int lane = threadIdx.x & (WAVE - 1);
@@ -3036,6 +3039,9 @@ __device__ __forceinline__ void step_body(
   }
   if (wid == 0) {
     prof_stamp(S, 0);
+#ifdef LNW_DIAG
+    prof_put(S, 13, t_entry);  // the kernel's first instruction (quiet workgroups: phase S reuses the slot)
+#endif
     // XCC id (hwreg 20, bits 3:0) and HW_ID (hwreg 4: CU, SH, SE) of this workgroup
     prof_put(S, 30, (unsigned long long)__builtin_amdgcn_s_getreg((3 << 11) | 20));
     prof_put(S, 31, (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4));
@@ -3511,6 +3517,39 @@ __device__ __forceinline__ void step_body(
   else write_obs(P, S, c, duct_col, obs_b, obs_r, env0, nenv, false);
 }
 
+// The step kernels' arguments (KParams, KState and eight pointers: 872 B, then
+// the grid size the runtime appends) span 14 cache lines of a buffer that is
+// new for every launch, so each line's first scalar load misses every cache.
+// The compiler fetches them where it first needs them: left to it, five to eight
+// of those misses stand in series before the first state load (s_load,
+// s_waitcnt lgkmcnt(0), s_load of the next line, ...), 2.2 us from the kernel's
+// first instruction to stamp 0 at 65 536 envs and 2.1 us at 8 192 (DESIGN.md,
+// "The step kernels' arguments").
+// One dword of every line requested back to back as the kernel's first
+// instructions puts the misses in flight together; the wait that follows costs
+// one round trip, and the compiler's own loads then hit the scalar cache. The
+// values are discarded (the registers are free again after the wait, which is
+// inside the statement: nothing is left in flight past it).
+__device__ __forceinline__ void kernarg_lines_prefetch() {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const auto ka = __builtin_amdgcn_kernarg_segment_ptr();
+  uint32_t t0, t1, t2, t3, t4, t5, t6, t7, t8, t9, t10, t11, t12, t13;
+  asm volatile(
+      "s_load_dword %0, %14, 0x0\n\ts_load_dword %1, %14, 0x40\n\ts_load_dword %2, %14, 0x80\n\t"
+      "s_load_dword %3, %14, 0xc0\n\ts_load_dword %4, %14, 0x100\n\ts_load_dword %5, %14, 0x140\n\t"
+      "s_load_dword %6, %14, 0x180\n\ts_load_dword %7, %14, 0x1c0\n\ts_load_dword %8, %14, 0x200\n\t"
+      "s_load_dword %9, %14, 0x240\n\ts_load_dword %10, %14, 0x280\n\ts_load_dword %11, %14, 0x2c0\n\t"
+      "s_load_dword %12, %14, 0x300\n\ts_load_dword %13, %14, 0x340\n\t"
+      "s_waitcnt lgkmcnt(0)"
+      : "=&s"(t0), "=&s"(t1), "=&s"(t2), "=&s"(t3), "=&s"(t4), "=&s"(t5), "=&s"(t6), "=&s"(t7), "=&s"(t8),
+        "=&s"(t9), "=&s"(t10), "=&s"(t11), "=&s"(t12), "=&s"(t13)
+      : "s"(ka));
+  // (the compiler's own argument loads stay behind the statement: hoisted above it,
+  // their round trip would come first and the lines' misses after it)
+  __builtin_amdgcn_sched_barrier(0);
+#endif
+}
+
 // One step of every env (lnw_step; lnw_step_seq makes one launch per step)
 // SL: quiet workgroups of up to 128 / NB envs write their rows in two slabs
 // (step_qdirect; a separate instantiation, so the one-slab kernels keep their code)
@@ -3518,7 +3557,17 @@ template <int NB, int NR, bool CW = false, bool REFW = false, int UN = 1, bool P
 __global__ __launch_bounds__(NB > 0 && EPW == WAVE ? 2 * WAVE * UN : WAVE, NB > 0 ? 2 : 1) void step_kernel(
     KParams P, KState S, void *actions, const uint8_t *row_kind, float *obs_b, float *obs_r,
     float *rew_b, float *rew_r, int32_t *done_out, float *cog_out) {
+#ifdef LNW_DIAG
+  // diagnostics: the clock before the argument loads, so LNW_PROF shows what the
+  // prologue costs up to stamp 0 (prof_report: "entry")
+  const unsigned long long t_entry = __builtin_amdgcn_s_memrealtime();
+  kernarg_lines_prefetch();
+  step_body<NB, NR, CW, REFW, UN, PS, SL>(P, S, actions, row_kind, obs_b, obs_r, rew_b, rew_r, done_out, cog_out,
+                                          t_entry);
+#else
+  kernarg_lines_prefetch();
   step_body<NB, NR, CW, REFW, UN, PS, SL>(P, S, actions, row_kind, obs_b, obs_r, rew_b, rew_r, done_out, cog_out);
+#endif
 }
 
 #include "lnw_group.inc"
@@ -3932,6 +3981,10 @@ struct lnw_handle {
   int device = 0;
   lnw_params params{};
   KParams kp{};
+  // device copies of every distinct cold block this handle has launched with,
+  // each written once and kept until lnw_destroy (cold_commit)
+  struct ColdSlot { KCold host; KCold *dev; };
+  std::vector<ColdSlot> cold_slots;
   int E = 0, nb = 0, nr = 0, A = 0, T = 0, nmax = 0;
   long long env_base = 0;
   int G = 0, W16 = 0;
@@ -3989,13 +4042,52 @@ KState make_state(lnw_handle *h) {
   s.pos = h->pos; s.radar = h->radar; s.miss = h->miss; s.mkind = h->mkind; s.alive = h->alive;
   s.type = h->type; s.steps = h->steps; s.dist_lz = h->dist_lz; s.tl_cnt = h->tl_cnt; s.tl = h->tl;
   s.duct = h->duct; s.envi = h->envi; s.rng = h->rng; s.err = h->err;
-  s.bear_val = h->bear_val; s.bear_ship = h->bear_ship; s.atan_deg = h->d_atan;
-  s.grid = h->d_grid; s.gridf = h->d_gridf; s.winf = h->d_winf; s.dummy = h->d_dummy; s.prof = nullptr; s.ana = h->ana; s.ctr = h->ctr; s.mask2 = h->d_mask2; s.mvtab = h->d_mvtab; s.lostab = h->d_lostab;
-  s.tape = h->tape; s.tape_off = h->tape_off;
-  s.sp_types = h->sp_types; s.sp_pos = h->sp_pos; s.sp_randls = h->sp_randls;
-  s.sp_pos_env = h->sp_pos_env_on ? h->sp_pos_env : nullptr;
+  s.atan_deg = h->d_atan;
+  s.grid = h->d_grid; s.gridf = h->d_gridf; s.winf = h->d_winf; s.dummy = h->d_dummy; s.prof = nullptr; s.cold = nullptr; s.mask2 = h->d_mask2; s.mvtab = h->d_mvtab; s.lostab = h->d_lostab;
   s.nmax = h->nmax;
   return s;
+}
+
+// The device block holding the handle's current cold values (KCold), for the
+// launch about to be made. Blocks are versioned, never rewritten: a set of
+// values not seen before gets a block of its own, written (a blocking copy)
+// before this returns, and launches made from now on point to it; launches
+// already queued, and captured graphs, keep reading the block they were given,
+// which stays as it was until lnw_destroy. So no setter has to wait for the
+// device, and a value set back to an earlier one (counters or analytics
+// toggled) reuses that block. Every entry point that launches a kernel taking KState goes
+// through here (launch_state), so whatever changed the handle (a setter,
+// lnw_reset's spawn spec, lnw_set_state) is picked up; the setters also commit
+// at once, so that a step captured into a graph right after them finds its
+// block ready (no allocation while capturing).
+int cold_commit(lnw_handle *h, ColdPtr *out) {
+  KCold c;
+  memset(&c, 0, sizeof c);
+  c.ana = h->ana;
+  c.tape = h->tape; c.tape_off = h->tape_off;
+  c.sp_types = h->sp_types; c.sp_pos = h->sp_pos; c.sp_randls = h->sp_randls;
+  c.sp_pos_env = h->sp_pos_env_on ? h->sp_pos_env : nullptr;
+  c.bear_val = h->bear_val; c.bear_ship = h->bear_ship;
+  c.ctr = h->ctr;
+  // newest first: the current block is almost always the last one made
+  for (size_t i = h->cold_slots.size(); i-- > 0;)
+    if (memcmp(&h->cold_slots[i].host, &c, sizeof c) == 0) {
+      if (out) *out = (ColdPtr)h->cold_slots[i].dev;
+      return 0;
+    }
+  KCold *d = nullptr;
+  HIPCHK(hipSetDevice(h->device));
+  if (int rc = dalloc(h, &d, 1)) return rc;
+  HIPCHK(hipMemcpy(d, &c, sizeof c, hipMemcpyHostToDevice));
+  h->cold_slots.push_back({c, d});
+  if (out) *out = (ColdPtr)d;
+  return 0;
+}
+
+// A launch's KState: the handle's arrays and the cold block's pointer.
+int launch_state(lnw_handle *h, KState &s) {
+  s = make_state(h);
+  return cold_commit(h, &s.cold);
 }
 
 size_t step_lds_bytes(const lnw_handle *h) {
@@ -4269,6 +4361,23 @@ void prof_report(lnw_handle *h, hipStream_t st, int nwg) {
                       "rows staged %.2f, stored %.2f us\n",
               nd, q0 / nd * us, q1 / nd * us, rb / nd * us, rc / nd * us);
   }
+#ifdef LNW_DIAG
+  {  // quiet workgroups: the kernel's first instruction (slot 13) to stamp 0, and stamp 0 to phase L's end
+    double se = 0, sl = 0, me = 0;
+    int ne = 0;
+    for (int w = 0; w < nwg; w++) {
+      const unsigned long long *r = &t[(size_t)w * PROF_SLOTS];
+      if (!r[14] || !r[13] || r[13] > r[0]) continue;
+      ne++;
+      se += (double)(r[0] - r[13]);
+      sl += (double)(r[4] - r[0]);
+      if ((double)(r[0] - r[13]) > me) me = (double)(r[0] - r[13]);
+    }
+    if (ne)
+      fprintf(stderr, "[lnw prof] entry -> stamp 0 %.3f us (max %.2f), stamp 0 -> phase-L end %.3f us (%d quiet records)\n",
+              se / ne * us, me * us, sl / ne * us, ne);
+  }
+#endif
   if (nq)
     fprintf(stderr, "[lnw prof] quiet workgroups %d: M %.2f us, A*+barrier %.2f us, quiet test %.2f us, Q+barrier %.2f us; "
                     "tail: rewards %.2f, cog %.2f, env_tail+outputs %.2f us\n",
@@ -4292,11 +4401,11 @@ const char *lnw_last_error(void) { return g_err.c_str(); }
 
 int lnw_set_analytics(lnw_handle *h, const lnw_analytics *a) {
   if (!h) return fail(LNW_EINVAL, "null handle");
-  if (!a) { h->ana = lnw_analytics{}; return 0; }
+  if (!a) { h->ana = lnw_analytics{}; return cold_commit(h, nullptr); }
   if ((a->eng_log && (!a->eng_count || a->eng_cap < 0)) || (a->ew_log && (!a->ew_count || a->ew_cap < 0)))
     return fail(LNW_EINVAL, "analytics log without a counter or with a negative capacity");
   h->ana = *a;
-  return 0;
+  return cold_commit(h, nullptr);
 }
 
 int lnw_hit_tables(double *tab64, float *tab32) {
@@ -4565,7 +4674,7 @@ int lnw_set_rng(lnw_handle *h, int32_t mode, uint64_t seed, const double *tape_d
   h->tape = tape_dev;
   h->tape_off = (const long long *)tape_off_dev;
   HIPCHK(hipMemset(h->rng, 0, sizeof(unsigned long long) * h->E));
-  return 0;
+  return cold_commit(h, nullptr);
 }
 
 // Validate a spawn spec's ship types (blue then red) and derive what the
@@ -4625,7 +4734,8 @@ int lnw_reset(lnw_handle *h, const uint8_t *env_mask_dev, const lnw_spawn *spawn
     HIPCHK(hipMemcpyAsync(h->sp_pos_env, pos_dev, n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
   }
   h->sp_pos_env_on = pos_dev != nullptr;
-  KState s = make_state(h);
+  KState s;
+  if (int rc = launch_state(h, s)) return rc;
   reset_kernel<<<(h->E + 255) / 256, 256, 0, st>>>(h->kp, s, env_mask_dev);
   HIPCHK(hipGetLastError());
   return 0;
@@ -4651,7 +4761,8 @@ int step_launch(lnw_handle *h, void *actions_dev, int32_t action_dtype,
   k.no_obs = obs_blue_dev == nullptr ? 1 : 0;
   k.dbg_skip = h->dbg_skip;
   k.store_wt = h->store_wt;
-  KState s = make_state(h);
+  KState s;
+  if (int rc = launch_state(h, s)) return rc;
   k.qdirect = step_qdirect(h, k.epw) ? 1 : 0;
   size_t lds = step_launch_lds_bytes(h, k.epw);
   dim3 grid((h->E + k.epw - 1) / k.epw), block(WAVE);
@@ -4779,7 +4890,8 @@ int lnw_observe_ex(lnw_handle *h, int32_t agent, float *obs_blue_dev, int64_t bl
       (red_env_stride && (red_env_stride < row_r || red_env_stride % 4)))
     return fail(LNW_EINVAL, "env stride: 0, or a multiple of 4 floats of at least the side's n * D");
   if (((uintptr_t)obs_blue_dev | (uintptr_t)obs_red_dev) & 15) return fail(LNW_EINVAL, "rows must be 16-B aligned");
-  KState s = make_state(h);
+  KState s;
+  if (int rc = launch_state(h, s)) return rc;
   size_t lds = step_lds_bytes(h);
   dim3 grid((h->E + h->kp.epw - 1) / h->kp.epw), block(WAVE);
   hipStream_t st = (hipStream_t)stream;
@@ -4958,13 +5070,13 @@ int lnw_set_state(lnw_handle *h, const void *src, int64_t nbytes, void *stream) 
   if (hd.rng_mode == LNW_RNG_PHILOX) h->kp.seed = hd.seed;
   for (int i = 0; i < 2; i++) { h->kp.box_lo[i] = hd.box_lo[i]; h->kp.box_hi[i] = hd.box_hi[i]; }
   h->sp_pos_env_on = hd.pos_env_on != 0;
-  return 0;
+  return cold_commit(h, nullptr);
 }
 
 int lnw_set_counters(lnw_handle *h, uint64_t *counters_dev) {
   if (!h) return fail(LNW_EINVAL, "null handle");
   h->ctr = (unsigned long long *)counters_dev;
-  return 0;
+  return cold_commit(h, nullptr);
 }
 
 int lnw_set_reward_dtype(lnw_handle *h, int32_t f64) {
@@ -5023,7 +5135,8 @@ int lnw_move_batch(lnw_handle *h, const int8_t *types_dev, const int16_t *pos_de
     return fail(LNW_EINVAL, "null argument");
   if (!h->terrain) return fail(LNW_ESTATE, "lnw_load_terrain must be called first");
   if (n <= 0) return 0;
-  KState s = make_state(h);
+  KState s;
+  if (int rc = launch_state(h, s)) return rc;
   move_batch_kernel<<<(unsigned)((n + WAVE - 1) / WAVE), WAVE, 0, (hipStream_t)stream>>>(
       h->kp, s, types_dev, pos_dev, act_dev, is_f32_dev, n, rounded_dev, ok_dev);
   HIPCHK(hipGetLastError());
@@ -5035,7 +5148,8 @@ int lnw_path_query(lnw_handle *h, const int8_t *types_dev, const int16_t *start_
   if (!h || !types_dev || !start_dev || !target_dev || !out_dev) return fail(LNW_EINVAL, "null argument");
   if (!h->terrain) return fail(LNW_ESTATE, "lnw_load_terrain must be called first");
   if (n <= 0) return 0;
-  KState s = make_state(h);
+  KState s;
+  if (int rc = launch_state(h, s)) return rc;
   path_query_kernel<<<(unsigned)((n + WAVE - 1) / WAVE), WAVE, 0, (hipStream_t)stream>>>(
       h->kp, s, types_dev, start_dev, target_dev, n, out_dev);
   HIPCHK(hipGetLastError());
@@ -5046,7 +5160,8 @@ int lnw_los_query(lnw_handle *h, const int16_t *pairs_dev, int64_t n, uint8_t *o
   if (!h || !pairs_dev || !out_dev) return fail(LNW_EINVAL, "null argument");
   if (!h->terrain) return fail(LNW_ESTATE, "lnw_load_terrain must be called first");
   if (n <= 0) return 0;
-  KState s = make_state(h);
+  KState s;
+  if (int rc = launch_state(h, s)) return rc;
   los_query_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(h->kp, s, pairs_dev, n, out_dev);
   HIPCHK(hipGetLastError());
   return 0;
