@@ -61,7 +61,7 @@ struct KParams {
 
 // Cold block: the part of the device state that only the loud (phase S / O),
 // in-kernel reset, tape-RNG and analytics paths read. One device-resident copy
-// per distinct set of values and handle (lnw_kernels.hip: cold_commit); the
+// per distinct set of values and handle (lnw_host.inc: cold_commit); the
 // kernels get a pointer to it instead of the values, which keeps them out of
 // the step kernels' argument segment.
 struct KCold {
@@ -122,6 +122,49 @@ __device__ inline int kind_promote(int a, int b) {
   if (a == K_F32 || b == K_F32) return K_F32;
   if (a == K_PYFLOAT || b == K_PYFLOAT) return K_PYFLOAT;
   return K_PYINT;
+}
+
+// take_action's salvo threshold round(engagement * missiles) (combatant.py:528),
+// rounded in the kind the two values promote to; the ship engages when it is
+// > 0. (nan/inf makes round() raise there: the caller tests isfinite.)
+// (miss by pointer: the column is read where it is used, after the promotion; by
+// value or by reference the read moves ahead of it in all twelve step kernels)
+__device__ __forceinline__ double salvo_size(double engagement, int keng, const uint8_t *miss, int mk) {
+  if (kind_promote(keng, mk) == K_F32) return (double)rintf((float)engagement * (float)*miss);
+  return rint(engagement * (double)*miss);
+}
+
+// The missiles one shot of fire_missile fires (combatant.py:620-628): of the
+// `miss` left (value kind mk), round(miss * salvo) in the kind the two promote
+// to — in DISCRETE mode the salvo itself, doubled unless the ship is small —
+// and at most what is left (then in the magazine's kind). Returns the number as
+// the reference holds it, its kind in kn; the caller takes (int) of it off the
+// magazine and promotes the magazine's kind by kn.
+// (type by reference: the column is read in DISCRETE mode only)
+__device__ __forceinline__ double missiles_fired(int discrete, const uint8_t &type, double salvo, int ksalvo,
+                                                 int miss, int mk, int &kn) {
+  double num;
+  if (!discrete) {
+    if (kind_promote(mk, ksalvo) == K_F32) {
+      num = (double)rintf((float)miss * (float)salvo);
+      kn = K_F32;
+    } else {
+      num = rint((double)miss * salvo);
+      kn = K_F64;  // np.round -> np.float64
+    }
+  } else {
+    num = type == T_SMALL ? salvo : salvo * 2.0;
+    kn = K_PYINT;
+  }
+  if (num > (double)miss) { num = (double)miss; kn = mk; }
+  return num;
+}
+
+// take_action's radar = round(a0) (combatant.py:558) as the int32 column holds
+// it, for a finite a0 (the caller tests isfinite, where round() raises)
+__device__ __forceinline__ int radar_setting(double a0) {
+  const double r = rint(a0);
+  return (int)fmin(fmax(r, -2147483648.0), 2147483647.0);
 }
 
 // --------------------------------------------------------------------------

@@ -199,22 +199,8 @@ __device__ __forceinline__ int fire_group_chunk(Ctx &X, int a, int mine, int nq,
     const int u = __builtin_ctz(msm);
     msm &= msm - 1;
     if (miss == 0) break;  // no missiles: this shot and every later one return without a draw
-    double num;
     int kn;
-    if (!P.discrete) {
-      const int kp = kind_promote(mk, ksalvo);
-      if (kp == K_F32) {
-        num = (double)rintf((float)miss * (float)salvo);
-        kn = K_F32;
-      } else {
-        num = rint((double)miss * salvo);
-        kn = K_F64;
-      }
-    } else {
-      num = COLB(c.type, a) == T_SMALL ? salvo : salvo * 2.0;
-      kn = K_PYINT;
-    }
-    if (num > (double)miss) { num = (double)miss; kn = mk; }
+    const double num = missiles_fired(P.discrete, COLB(c.type, a), salvo, ksalvo, miss, mk, kn);
     int n = (int)num;
     miss = (miss - n) & 0xff;  // (the uint8 column)
     mk = kind_promote(mk, kn);
@@ -278,7 +264,7 @@ __device__ __forceinline__ void group_pair_tables(Ctx &X, int sub, GSide (&gs)[2
       const uint32_t qn = COLW(c.pos_new, j);
       if (qn & 0x80000000u) pj = qn & 0x7fffffffu;
       const double a0 = COLW(c.act0, j);
-      radj = isfinite(a0) ? (int)fmin(fmax(rint(a0), -2147483648.0), 2147483647.0) : 0;
+      radj = isfinite(a0) ? radar_setting(a0) : 0;
     }
     g.pos = mine ? pj : 0xffffffffu;
     {
@@ -835,11 +821,7 @@ __global__ __launch_bounds__(GEPW * GL) void step_group_kernel(
         const double engagement = P.discrete ? rint(a1) : a1;
         const int keng = P.discrete ? K_PYINT : kind;
         const int mk = COLB(c.mkind, a);
-        double thr_v;
-        if (kind_promote(keng, mk) == K_F32)
-          thr_v = (double)rintf((float)engagement * (float)COLB(c.miss_cur, a));
-        else
-          thr_v = rint(engagement * (double)COLB(c.miss_cur, a));
+        double thr_v = salvo_size(engagement, keng, &COLB(c.miss_cur, a), mk);
         // round(nan/inf) of engagement * missiles raises (combatant.py:528): flagged, no engagement
         if (!isfinite(thr_v)) { X.rng.err |= LNW_ERRF_NAN_ROUND; thr_v = 0.0; }
         engage = thr_v > 0.0;
@@ -871,10 +853,7 @@ __global__ __launch_bounds__(GEPW * GL) void step_group_kernel(
         }
         if (side) ev[6] += destroyed; else ev[5] += destroyed;
         if (!isfinite(a0)) { X.rng.err |= LNW_ERRF_NAN_ROUND; COLW(c.radar_cur, a) = 0; }
-        else {
-          const double rr = rint(a0);
-          COLW(c.radar_cur, a) = (int)fmin(fmax(rr, -2147483648.0), 2147483647.0);
-        }
+        else COLW(c.radar_cur, a) = radar_setting(a0);
         const uint32_t pn = COLW(c.pos_new, a);
         moved = (pn & 0x80000000u) != 0;
         if (moved) COLW(c.pos_cur, a) = pn & 0x7fffffffu;

@@ -2,6 +2,12 @@
 // environment step. See include/lnw.h for the boundary and DESIGN.md for the
 // layout/roofline discussion.
 //
+// One translation unit in pieces: this file holds the step, observe and reset
+// kernels and includes lnw_quiet.inc (quiet workgroups), lnw_turn.inc (one
+// ship's turn of phase S), lnw_group.inc (the group kernel), lnw_tables.inc
+// (terrain-table builders, batch / query kernels) and lnw_host.inc (the host
+// side and the C-ABI, which launches the kernel templates).
+//
 // Step structure (one 64-lane wavefront = one workgroup = 64 environments):
 //   L  coalesced load of the agent-major SoA state into padded LDS columns
 //   M  movement feasibility for every (env, agent): move target in the row's
@@ -1508,7 +1514,7 @@ __device__ inline void pair_tables_t(Ctx &X) {
     int rb;
     if constexpr (STEP) {  // blue's radar once it has acted (take_action)
       const double a0 = COLW(c.act0, i);
-      rb = isfinite(a0) ? (int)fmin(fmax(rint(a0), -2147483648.0), 2147483647.0) : 0;
+      rb = isfinite(a0) ? radar_setting(a0) : 0;
     } else {
       rb = COLW(c.radar_cur, i);
     }
@@ -1678,22 +1684,8 @@ __device__ inline bool fire_dev(Ctx &X, int a, int tx, int ty, double salvo, int
     X.rng.uniform2(u1, u2);
     bool detected = !(u1 < (COLW(c.radar_cur, t) == 1 ? P.det_q[0] : P.det_q[1]));
     int hp = detected ? 0 : 1;
-    double num;
     int kn;
-    if (!P.discrete) {
-      int kp = kind_promote(mk, ksalvo);
-      if (kp == K_F32) {
-        num = (double)rintf((float)miss * (float)salvo);
-        kn = K_F32;
-      } else {
-        num = rint((double)miss * salvo);
-        kn = K_F64;  // np.round -> np.float64
-      }
-    } else {
-      num = COLB(c.type, a) == T_SMALL ? salvo : salvo * 2.0;
-      kn = K_PYINT;
-    }
-    if (num > (double)miss) { num = (double)miss; kn = mk; }
+    const double num = missiles_fired(P.discrete, COLB(c.type, a), salvo, ksalvo, miss, mk, kn);
     n = (int)num;
     COLB(c.miss_cur, a) = (uint8_t)(miss - n);
     COLB(c.mkind, a) = (uint8_t)kind_promote(mk, kn);
@@ -1745,21 +1737,8 @@ __device__ inline int fire_draws(Ctx &X, int a, double salvo, int ksalvo) {
     const uint32_t pt = COLW(c.pos_cur, t);
     const int dx = pos_x(pt) - pos_x(pa), dy = pos_y(pt) - pos_y(pa);
     if (dx * dx + dy * dy < 4 || miss == 0) continue;  // main gun, or no missiles: no draw
-    double num;
     int kn;
-    if (!P.discrete) {
-      if (kind_promote(mk, ksalvo) == K_F32) {
-        num = (double)rintf((float)miss * (float)salvo);
-        kn = K_F32;
-      } else {
-        num = rint((double)miss * salvo);
-        kn = K_F64;
-      }
-    } else {
-      num = COLB(c.type, a) == T_SMALL ? salvo : salvo * 2.0;
-      kn = K_PYINT;
-    }
-    if (num > (double)miss) { num = (double)miss; kn = mk; }
+    const double num = missiles_fired(P.discrete, COLB(c.type, a), salvo, ksalvo, miss, mk, kn);
     miss = (miss - (int)num) & 0xff;
     mk = kind_promote(mk, kn);
     nd += 2;
@@ -3176,7 +3155,8 @@ __device__ __forceinline__ void step_body(
     if constexpr (PS && ST && CW && NB == 4 && NR == 4) {
       // one ship's turn (take_action, get_obs, calculate_reward: game.py:338-381)
       // on the view X.c: wave 0's is the workgroup's columns, the split's wave 1
-      // its own (the parameters shadow the loop state they update)
+      // its own (the parameters shadow the loop state they update, so the turn's
+      // text, lnw_turn.inc, is the same here and in the plain loop below)
       // (the hit state is copied in and out: a runtime index into an array behind a
       // reference would keep it in scratch)
       auto turn = [&](Ctx &X, int a, Neut &Nio, int (&evio)[8], int (&hio)[2], int &bsx, int &bsy, int &nbp,
@@ -3184,109 +3164,7 @@ __device__ __forceinline__ void step_body(
         Cols &c = X.c;
         Neut N = Nio;
         int ev[8] = {0, 0, 0, 0, 0, 0, 0, 0}, hits[2] = {0, 0};
-        const bool al = COLB(c.alive0, a) != 0;  // sunk ships skip their turn (reward 0)
-        const int side = a >= nb;
-        bool engage = false, moved = false;
-        int destroyed = 0;
-        t0 = prof_now(S);
-        if (al) {
-          uint32_t p0 = COLW(c.pos_cur, a);
-          if (!side) {
-            if (P.side_blue) { bsx += pos_x(p0); bsy += pos_y(p0); nbp++; }
-          } else {
-            rsx += pos_x(p0); rsy += pos_y(p0); nrp++;
-          }
-          size_t row = ((size_t)env * A + a) * 4;
-          double a0 = COLW(c.act0, a), a1 = COLW(c.act1, a);
-          int kind = COLB(c.akind, a);
-          // untrained red: random salvo (game.py:375-379), written back in place
-          if (side && !P.trained_red) {
-            if (X.rng.uniform() < P.red_aggression) {
-              double v = X.rng.uniform();
-              if (dt == LNW_ACT_F32) { float f = (float)v; ((float *)actions)[row + 1] = f; a1 = f; }
-              else if (dt == LNW_ACT_F64) {
-                if (kind == K_F32) v = (double)(float)v;
-                ((double *)actions)[row + 1] = v; a1 = v;
-              } else { ((int32_t *)actions)[row + 1] = 0; a1 = 0.0; }
-            }
-          }
-          // take_action (combatant.py:501-565)
-          double engagement = P.discrete ? rint(a1) : a1;
-          int keng = P.discrete ? K_PYINT : kind;
-          int mk = COLB(c.mkind, a);
-          double thr_v;
-          if (kind_promote(keng, mk) == K_F32)
-            thr_v = (double)rintf((float)engagement * (float)COLB(c.miss_cur, a));
-          else
-            thr_v = rint(engagement * (double)COLB(c.miss_cur, a));
-          // round(nan/inf) of engagement * missiles raises (combatant.py:528): flagged, no engagement
-          if (!isfinite(thr_v)) { X.rng.err |= LNW_ERRF_NAN_ROUND; thr_v = 0.0; }
-          engage = thr_v > 0.0;
-          int tn = (int)COLW(c.tcnt, a);
-          if (engage && tn > 0 && !(P.dbg_skip & 65536)) {  // (bit 16: diagnostics, no fire)
-            const uint16_t *tl = S.tl + (size_t)a * P.T * E + env;
-            if constexpr (CW) {
-              // contact variant: the list read 8 entries at a time, the loads of a
-              // chunk in flight together (packed in a register pair: a runtime index
-              // into a register array would put it in scratch)
-              for (int q0 = 0; q0 < tn; q0 += 8) {
-                uint64_t pk0 = 0, pk1 = 0;
-#pragma unroll
-                for (int u = 0; u < 8; u++) {
-                  const uint64_t v = q0 + u < tn ? (uint64_t)tl[(size_t)(q0 + u) * E] : 0ull;
-                  if (u < 4) pk0 |= v << (16 * u);
-                  else pk1 |= v << (16 * (u - 4));
-                }
-                const int nq = tn - q0 < 8 ? tn - q0 : 8;
-                for (int u = 0; u < nq; u++) {
-                  const uint16_t tg = (uint16_t)((u < 4 ? pk0 : pk1) >> (16 * (u & 3)));
-                  if (fire_dev(X, a, tg & 0xff, tg >> 8, engagement, keng, N)) destroyed++;
-                }
-              }
-            } else {
-              uint16_t nx = tl[0];  // the next target's load is in flight while one fires
-              for (int q = 0; q < tn; q++) {
-                const uint16_t tg = nx;
-                if (q + 1 < tn) nx = tl[(size_t)(q + 1) * E];
-                if (fire_dev(X, a, tg & 0xff, tg >> 8, engagement, keng, N)) destroyed++;
-              }
-            }
-          }
-          if (side) ev[6] += destroyed; else ev[5] += destroyed;
-          if (!isfinite(a0)) { X.rng.err |= LNW_ERRF_NAN_ROUND; COLW(c.radar_cur, a) = 0; }
-          else {
-            double rr = rint(a0);
-            COLW(c.radar_cur, a) = (int)fmin(fmax(rr, -2147483648.0), 2147483647.0);
-          }
-          uint32_t pn = COLW(c.pos_new, a);
-          moved = (pn & 0x80000000u) != 0;
-          if (moved) COLW(c.pos_cur, a) = pn & 0x7fffffffu;
-        }
-        tp[0] += prof_now(S) - t0;
-        t0 = prof_now(S);
-        if (al && !(P.dbg_skip & 128)) {
-          if constexpr (REFW) march_pairs_ref(X, a);
-          if constexpr (ST) {
-            if (!side) get_obs_t<NB, NR, CW>(X, a, 0, NB);
-            else get_obs_t<NR, NB, CW>(X, a, NB, 0);
-          } else {
-            get_obs_dev(X, a);
-          }
-        }
-        tp[2] += prof_now(S) - t0;
-        t0 = prof_now(S);
-        double r = 0.0;
-        if (al && !(P.dbg_skip & 256)) r = reward_dev(X, a, moved, engage, destroyed);
-        COLW(c.reward, a) = r;
-        if (al) {
-          if (!side) {
-            if (P.side_blue ? destroyed > 0 : engage) COLB(c.eng, a) = 1;
-          } else {
-            if (!P.trained_red ? engage : destroyed > 1) COLB(c.eng, a) = 1;
-          }
-          hits[side] += destroyed;
-        }
-        tp[3] += prof_now(S) - t0;
+#include "lnw_turn.inc"
         Nio = N;
         evio[5] += ev[5];
         evio[6] += ev[6];
@@ -3311,7 +3189,7 @@ __device__ __forceinline__ void step_body(
               const uint32_t pn = COLW(c.pos_new, a);
               if (pn & 0x80000000u) p = pn & 0x7fffffffu;
               const double a0 = COLW(c.act0, a);
-              r = !isfinite(a0) ? 0 : (int)fmin(fmax(rint(a0), -2147483648.0), 2147483647.0);
+              r = !isfinite(a0) ? 0 : radar_setting(a0);
             }
             COLW(cr.pos_cur, a) = p;
             COLW(cr.radar_cur, a) = r;
@@ -3323,9 +3201,7 @@ __device__ __forceinline__ void step_body(
             const double engagement = P.discrete ? rint(a1) : a1;
             const int keng = P.discrete ? K_PYINT : kind;
             const int mk = COLB(c.mkind, a);
-            const double thr_v = kind_promote(keng, mk) == K_F32
-                                     ? (double)rintf((float)engagement * (float)COLB(c.miss_cur, a))
-                                     : rint(engagement * (double)COLB(c.miss_cur, a));
+            const double thr_v = salvo_size(engagement, keng, &COLB(c.miss_cur, a), mk);
             if (isfinite(thr_v) && thr_v > 0.0 && COLW(c.tcnt, a) > 0 && !(P.dbg_skip & 65536))
               nd += fire_draws(X, a, engagement, keng);
           }
@@ -3395,111 +3271,9 @@ __device__ __forceinline__ void step_body(
           if (a < 8) prof_stamp(S, 6 + a);
         }
       }
-    } else {  // (the loop written out: behind a lambda it keeps state in scratch)
+    } else {  // (the turn in the loop itself: behind a lambda it keeps state in scratch)
       for (int a = 0; a < A; a++) {
-        const bool al = COLB(c.alive0, a) != 0;  // sunk ships skip their turn (reward 0)
-        const int side = a >= nb;
-        bool engage = false, moved = false;
-        int destroyed = 0;
-        t0 = prof_now(S);
-        if (al) {
-          uint32_t p0 = COLW(c.pos_cur, a);
-          if (!side) {
-            if (P.side_blue) { bsx += pos_x(p0); bsy += pos_y(p0); nbp++; }
-          } else {
-            rsx += pos_x(p0); rsy += pos_y(p0); nrp++;
-          }
-          size_t row = ((size_t)env * A + a) * 4;
-          double a0 = COLW(c.act0, a), a1 = COLW(c.act1, a);
-          int kind = COLB(c.akind, a);
-          // untrained red: random salvo (game.py:375-379), written back in place
-          if (side && !P.trained_red) {
-            if (X.rng.uniform() < P.red_aggression) {
-              double v = X.rng.uniform();
-              if (dt == LNW_ACT_F32) { float f = (float)v; ((float *)actions)[row + 1] = f; a1 = f; }
-              else if (dt == LNW_ACT_F64) {
-                if (kind == K_F32) v = (double)(float)v;
-                ((double *)actions)[row + 1] = v; a1 = v;
-              } else { ((int32_t *)actions)[row + 1] = 0; a1 = 0.0; }
-            }
-          }
-          // take_action (combatant.py:501-565)
-          double engagement = P.discrete ? rint(a1) : a1;
-          int keng = P.discrete ? K_PYINT : kind;
-          int mk = COLB(c.mkind, a);
-          double thr_v;
-          if (kind_promote(keng, mk) == K_F32)
-            thr_v = (double)rintf((float)engagement * (float)COLB(c.miss_cur, a));
-          else
-            thr_v = rint(engagement * (double)COLB(c.miss_cur, a));
-          // round(nan/inf) of engagement * missiles raises (combatant.py:528): flagged, no engagement
-          if (!isfinite(thr_v)) { X.rng.err |= LNW_ERRF_NAN_ROUND; thr_v = 0.0; }
-          engage = thr_v > 0.0;
-          int tn = (int)COLW(c.tcnt, a);
-          if (engage && tn > 0 && !(P.dbg_skip & 65536)) {  // (bit 16: diagnostics, no fire)
-            const uint16_t *tl = S.tl + (size_t)a * P.T * E + env;
-            if constexpr (CW) {
-              // contact variant: the list read 8 entries at a time, the loads of a
-              // chunk in flight together (packed in a register pair: a runtime index
-              // into a register array would put it in scratch)
-              for (int q0 = 0; q0 < tn; q0 += 8) {
-                uint64_t pk0 = 0, pk1 = 0;
-#pragma unroll
-                for (int u = 0; u < 8; u++) {
-                  const uint64_t v = q0 + u < tn ? (uint64_t)tl[(size_t)(q0 + u) * E] : 0ull;
-                  if (u < 4) pk0 |= v << (16 * u);
-                  else pk1 |= v << (16 * (u - 4));
-                }
-                const int nq = tn - q0 < 8 ? tn - q0 : 8;
-                for (int u = 0; u < nq; u++) {
-                  const uint16_t tg = (uint16_t)((u < 4 ? pk0 : pk1) >> (16 * (u & 3)));
-                  if (fire_dev(X, a, tg & 0xff, tg >> 8, engagement, keng, N)) destroyed++;
-                }
-              }
-            } else {
-              uint16_t nx = tl[0];  // the next target's load is in flight while one fires
-              for (int q = 0; q < tn; q++) {
-                const uint16_t tg = nx;
-                if (q + 1 < tn) nx = tl[(size_t)(q + 1) * E];
-                if (fire_dev(X, a, tg & 0xff, tg >> 8, engagement, keng, N)) destroyed++;
-              }
-            }
-          }
-          if (side) ev[6] += destroyed; else ev[5] += destroyed;
-          if (!isfinite(a0)) { X.rng.err |= LNW_ERRF_NAN_ROUND; COLW(c.radar_cur, a) = 0; }
-          else {
-            double rr = rint(a0);
-            COLW(c.radar_cur, a) = (int)fmin(fmax(rr, -2147483648.0), 2147483647.0);
-          }
-          uint32_t pn = COLW(c.pos_new, a);
-          moved = (pn & 0x80000000u) != 0;
-          if (moved) COLW(c.pos_cur, a) = pn & 0x7fffffffu;
-        }
-        tp[0] += prof_now(S) - t0;
-        t0 = prof_now(S);
-        if (al && !(P.dbg_skip & 128)) {
-          if constexpr (REFW) march_pairs_ref(X, a);
-          if constexpr (ST) {
-            if (!side) get_obs_t<NB, NR, CW>(X, a, 0, NB);
-            else get_obs_t<NR, NB, CW>(X, a, NB, 0);
-          } else {
-            get_obs_dev(X, a);
-          }
-        }
-        tp[2] += prof_now(S) - t0;
-        t0 = prof_now(S);
-        double r = 0.0;
-        if (al && !(P.dbg_skip & 256)) r = reward_dev(X, a, moved, engage, destroyed);
-        COLW(c.reward, a) = r;
-        if (al) {
-          if (!side) {
-            if (P.side_blue ? destroyed > 0 : engage) COLB(c.eng, a) = 1;
-          } else {
-            if (!P.trained_red ? engage : destroyed > 1) COLB(c.eng, a) = 1;
-          }
-          hits[side] += destroyed;
-        }
-        tp[3] += prof_now(S) - t0;
+#include "lnw_turn.inc"
         if (emit) publish_progress(&prog, a + 1);
         if (a < 8) prof_stamp(S, 6 + a);
       }
@@ -3696,1492 +3470,6 @@ __global__ void reset_kernel(KParams P, KState S, const uint8_t *mask) {
   if (r.err) S.err[env] |= r.err;
 }
 
-// ---------------------------------------------------------------------------
-// terrain structures
-// ---------------------------------------------------------------------------
-__global__ void build_mask_kernel(const uint8_t *grid, int G, int W16, int move_thr, int ew_thr,
-                                  uint32_t *mask2) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= G * W16) return;
-  int x = i / W16, w = i % W16;
-  uint32_t v = 0;
-  for (int b = 0; b < 16; b++) {
-    int y = w * 16 + b;
-    if (y >= G) break;
-    uint8_t g = grid[x * G + y];
-    v |= ((g > move_thr ? 1u : 0u) | (g > ew_thr ? 2u : 0u)) << (2 * b);
-  }
-  mask2[i] = v;
-}
+#include "lnw_tables.inc"
 
-// move table: check_path(start, start + off) for off in [-4,4]^2, per class
-// (mv_cls: Combatant speed 3, LandingShip, medium Combatant speed 2)
-constexpr int MV_CLASSES = 3;
-__global__ __launch_bounds__(64) void build_move_table_kernel(const uint32_t *mask2, int G, int W16,
-                                                              uint32_t *mvtab) {
-  __shared__ uint32_t open[OPEN_CAP * WAVE];
-  long long i = (long long)blockIdx.x * WAVE + threadIdx.x;
-  long long n = (long long)MV_CLASSES * G * G * MV_W * MV_W;
-  if (i >= n) return;
-  int off = (int)(i % (MV_W * MV_W));
-  long long cell = (i / (MV_W * MV_W)) % ((long long)G * G);
-  int cls = (int)(i / ((long long)MV_W * MV_W * G * G));
-  int sx = (int)(cell / G), sy = (int)(cell % G);
-  int tx = sx + off / MV_W - R_MV, ty = sy + off % MV_W - R_MV;
-  MaskBlocked mb{mask2, W16};
-  const int type = cls == 0 ? T_SMALL : (cls == 1 ? T_LS : T_MEDIUM);  // (mv_cls inverse)
-  bool feas = check_path_dev(mb, mb(sx, sy), G, type, sx, sy, tx, ty,
-                             open + threadIdx.x, WAVE);
-  if (feas) atomicOr(&mvtab[(cls * (long long)G * G + cell) * MV_WORDS + (off >> 5)], 1u << (off & 31));
-}
-
-// LOS table: for every origin cell and offset in [-40,40]^2, bit0 radar clear,
-// bit1 EW clear (full march, no early exit). The 2-bit terrain mask is staged
-// into LDS once per workgroup (mwords words, when it fits the launch's LDS),
-// and each workgroup then walks many (cell, row) items in a grid-stride loop,
-// so the mask is read once per resident workgroup rather than once per 256
-// items (G = 512: 64 KiB per workgroup).
-__global__ __launch_bounds__(256) void build_los_table_kernel(const uint32_t *mask2, int G, int W16,
-                                                              uint32_t *lostab, int mwords) {
-  uint32_t *lm = (uint32_t *)lds_dyn;
-  for (int w = threadIdx.x; w < mwords; w += blockDim.x) lm[w] = mask2[w];
-  __syncthreads();
-  const uint32_t *msk = mwords ? lm : mask2;
-  const long long n = (long long)G * G * LOS_W;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (long long)gridDim.x * blockDim.x) {
-    const int row = (int)(i % LOS_W);
-    const long long cell = i / LOS_W;
-    const int x1 = (int)(cell / G), y1 = (int)(cell % G);
-    const int x2 = x1 + row - R_LOS;
-    uint32_t words[LOS_ROW_WORDS] = {0, 0, 0, 0, 0, 0};
-    if (x2 >= 0 && x2 < G) {
-      for (int c = 0; c < LOS_W; c++) {
-        const int y2 = y1 + c - R_LOS;
-        if (y2 < 0 || y2 >= G) continue;
-        const uint32_t b = los_march<false>(msk, W16, x1, y1, x2, y2);
-        const int col = c * 2;
-        words[col >> 5] |= b << (col & 31);
-      }
-    }
-    uint32_t *dst = lostab + cell * LOS_CELL_WORDS + row * LOS_ROW_WORDS;
-#pragma unroll
-    for (int w = 0; w < LOS_ROW_WORDS; w++) dst[w] = words[w];
-  }
-}
-
-// ---------------------------------------------------------------------------
-// unit kernels
-// ---------------------------------------------------------------------------
-// lnw_los_batch (combatant.py:436-456 per ray): every workgroup first builds the
-// grid's 2-bit terrain mask (bit0 cell > move_thr, bit1 cell > ew_thr) in LDS,
-// then its waves march their share of the rays from it. A lane whose ray has
-// ended takes the wave's next unclaimed ray (ballot + popcount of the lanes
-// asking), so a wave advances at its lanes' mean ray length instead of
-// waiting on its longest ray; a ray stops early once both bits are blocked
-// (the result cannot change).
-constexpr int LB_THREADS = 256, LB_RAYS_PER_WAVE = 1024;
-__global__ __launch_bounds__(LB_THREADS) void los_batch_kernel(const uint8_t *grid, int G, const int16_t *pairs,
-                                                               long long n, int move_thr, int ew_thr, uint8_t *out) {
-  const int W16 = (G + 15) >> 4;
-  uint32_t *lm = (uint32_t *)lds_dyn;
-  for (int w = threadIdx.x; w < G * W16; w += LB_THREADS) {
-    const int x = w / W16, y0 = (w - x * W16) * 16;
-    uint32_t v = 0;
-    for (int b = 0; b < 16 && y0 + b < G; b++) {
-      const uint8_t g = grid[(size_t)x * G + y0 + b];
-      v |= ((g > move_thr ? 1u : 0u) | (g > ew_thr ? 2u : 0u)) << (2 * b);
-    }
-    lm[w] = v;
-  }
-  __syncthreads();
-  const int lane = threadIdx.x & (WAVE - 1);
-  const long long w0 = ((long long)blockIdx.x * (LB_THREADS / WAVE) + (threadIdx.x / WAVE)) * LB_RAYS_PER_WAVE;
-  const long long wend = w0 + LB_RAYS_PER_WAVE < n ? w0 + LB_RAYS_PER_WAVE : n;
-  long long next = w0;  // the wave's next unclaimed ray (uniform)
-  long long idx = -1;   // this lane's ray
-  int x = 0, y = 0, x2 = 0, y2 = 0, dx = 0, dy = 0, sx = 1, sy = 1, err = 0;
-  uint32_t blk = 0;
-  const unsigned long long below = (1ull << lane) - 1ull;
-  auto claim = [&]() {
-    const unsigned long long need = __ballot(idx < 0);
-    if (idx < 0) {
-      const long long k = next + __popcll(need & below);
-      if (k < wend) {
-        const uint64_t pr = *(const uint64_t *)(pairs + 4 * k);
-        x = (int16_t)(pr & 0xffffu);
-        y = (int16_t)((pr >> 16) & 0xffffu);
-        x2 = (int16_t)((pr >> 32) & 0xffffu);
-        y2 = (int16_t)(pr >> 48);
-        dx = abs(x2 - x);
-        dy = abs(y2 - y);
-        sx = x > x2 ? -1 : 1;
-        sy = y > y2 ? -1 : 1;
-        err = dx - dy;
-        blk = 0;
-        idx = k;
-      }
-    }
-    next += __popcll(need);
-  };
-  claim();
-  while (__any(idx >= 0)) {
-    if (idx >= 0) {
-#pragma unroll 4
-      for (int s = 0; s < 8; s++) {
-        blk |= cell_bits(lm, W16, x, y);
-        if (blk == 3u || (x == x2 && y == y2)) {
-          out[idx] = (uint8_t)((~blk) & 3u);
-          idx = -1;
-          break;
-        }
-        const int e2 = 2 * err;
-        if (e2 > -dy) { err -= dy; x += sx; }
-        if (e2 < dx) { err += dx; y += sy; }
-      }
-    }
-    if (next < wend) claim();
-  }
-}
-
-// grids whose mask does not fit the launch's LDS: one lane per ray from HBM
-__global__ void los_batch_global_kernel(const uint8_t *grid, int G, const int16_t *pairs, long long n,
-                                        int move_thr, int ew_thr, uint8_t *out) {
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  int x1 = pairs[4 * i], y1 = pairs[4 * i + 1], x2 = pairs[4 * i + 2], y2 = pairs[4 * i + 3];
-  int dx = abs(x2 - x1), dy = abs(y2 - y1);
-  int sx = x1 > x2 ? -1 : 1, sy = y1 > y2 ? -1 : 1;
-  int err = dx - dy;
-  bool rb = false, eb = false;
-  for (;;) {
-    uint8_t g = grid[x1 * G + y1];
-    rb |= g > move_thr;
-    eb |= g > ew_thr;
-    if (x1 == x2 && y1 == y2) break;
-    int e2 = 2 * err;
-    if (e2 > -dy) { err -= dy; x1 += sx; }
-    if (e2 < dx) { err += dx; y1 += sy; }
-  }
-  out[i] = (rb ? 0 : 1) | (eb ? 0 : 2);
-}
-
-__global__ __launch_bounds__(64) void astar_batch_kernel(const uint8_t *grid, int G, int thr,
-                                                         const int8_t *types, const int16_t *st,
-                                                         const int16_t *tg, long long n,
-                                                         int16_t *plen, int8_t *kind,
-                                                         uint8_t *feas) {
-  __shared__ uint32_t open[OPEN_CAP * WAVE];
-  long long i = (long long)blockIdx.x * WAVE + threadIdx.x;
-  if (i >= n) return;
-  int t = types[i];
-  int sx = st[2 * i], sy = st[2 * i + 1], tx = tg[2 * i], ty = tg[2 * i + 1];
-  GridBlocked gb{grid, G, thr};
-  if (abs(tx) > 500 || abs(ty) > 500 || sx < 0 || sy < 0 || sx >= G || sy >= G) {
-    plen[i] = -2; kind[i] = -1; feas[i] = 0;
-    return;
-  }
-  int k;
-  int len = astar_dev(gb, G, ship_speed(t), sx, sy, tx, ty, k, open + threadIdx.x, WAVE);
-  plen[i] = (int16_t)len;
-  kind[i] = (int8_t)k;
-  feas[i] = check_path_dev(gb, gb(sx, sy), G, t, sx, sy, tx, ty, open + threadIdx.x, WAVE) ? 1 : 0;
-}
-
-__global__ __launch_bounds__(64) void move_batch_kernel(KParams P, KState S, const int8_t *types,
-                                                        const int16_t *pos, const double *act,
-                                                        const uint8_t *is_f32, long long n,
-                                                        int32_t *rounded, uint8_t *ok) {
-  __shared__ uint32_t open[OPEN_CAP * WAVE];
-  long long i = (long long)blockIdx.x * WAVE + threadIdx.x;
-  if (i >= n) return;
-  int t = types[i];
-  int sx = pos[2 * i], sy = pos[2 * i + 1];
-  int nx, ny;
-  bool fin = move_target_dev(sx, sy, ship_speed(t), act[2 * i], act[2 * i + 1],
-                             is_f32[i] ? K_F32 : K_F64, nx, ny);
-  rounded[2 * i] = nx;
-  rounded[2 * i + 1] = ny;
-  bool f = fin && can_move_to_h(P, S, nx, ny) &&
-           check_path_h(P, S, t, sx, sy, nx, ny, open + threadIdx.x, WAVE);
-  ok[i] = f ? 1 : 0;
-}
-
-__global__ __launch_bounds__(64) void path_query_kernel(KParams P, KState S, const int8_t *types,
-                                                        const int16_t *st, const int16_t *tg,
-                                                        long long n, uint8_t *out) {
-  __shared__ uint32_t open[OPEN_CAP * WAVE];
-  long long i = (long long)blockIdx.x * WAVE + threadIdx.x;
-  if (i >= n) return;
-  out[i] = check_path_h(P, S, types[i], st[2 * i], st[2 * i + 1], tg[2 * i], tg[2 * i + 1],
-                        open + threadIdx.x, WAVE) ? 1 : 0;
-}
-
-__global__ void los_query_kernel(KParams P, KState S, const int16_t *pairs, long long n,
-                                 uint8_t *out) {
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  out[i] = (uint8_t)los_q(P, S, S.mask2, pairs[4 * i], pairs[4 * i + 1], pairs[4 * i + 2],
-                          pairs[4 * i + 3]);
-}
-
-__global__ void fill_uniform_kernel(float *out, long long n, unsigned long long seed,
-                                    unsigned long long offset) {
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  long long base = i * 4;
-  if (base >= n) return;
-  float u[4];
-  philox_u4(seed, (offset >> 2) + (unsigned long long)i, u);
-#pragma unroll
-  for (int k = 0; k < 4; k++)
-    if (base + k < n) out[base + k] = u[k];
-}
-
-// ===========================================================================
-// host side
-// ===========================================================================
-thread_local std::string g_err;
-
-int fail(int code, const std::string &msg) {
-  g_err = msg;
-  return code;
-}
-
-#define HIPCHK(expr)                                                                  \
-  do {                                                                                \
-    hipError_t _e = (expr);                                                           \
-    if (_e != hipSuccess)                                                             \
-      return fail(LNW_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(_e));    \
-  } while (0)
-
-void host_constants(KParams &k) {
-  const double base = std::sqrt((4.0 / 3.0) * 6370.0 * 2.0);
-  const int masts[2] = {15, 30};
-  for (int i = 0; i < 2; i++)
-    for (int j = 0; j < 2; j++) {
-      double d = base * (std::sqrt((double)masts[i] / 1000.0) + std::sqrt((double)masts[j] / 1000.0));
-      k.d5[i][j] = d / 5.0;
-    }
-  for (int i = 0; i < 2; i++)
-    k.den[i] = (base * (std::sqrt((double)masts[i] / 1000.0) + std::sqrt(15.0 / 1000.0))) / 5.0;
-  k.det_q[0] = 0.345 - 0.1;
-  k.det_q[1] = 0.345 + 0.1;
-  const double ps[2] = {0.45, 0.63};
-  for (int h = 0; h < 2; h++)
-    for (int n = 0; n < 9; n++) {
-      k.hit64[h][n] = 1.0 - std::pow(1.0 - ps[h], (double)n);
-      float pn = powf((float)(1.0 - ps[h]), (float)n);
-      k.hit32[h][n] = 1.0f - pn;
-    }
-}
-
-}  // namespace
-
-struct lnw_handle {
-  int device = 0;
-  lnw_params params{};
-  KParams kp{};
-  // device copies of every distinct cold block this handle has launched with,
-  // each written once and kept until lnw_destroy (cold_commit)
-  struct ColdSlot { KCold host; KCold *dev; };
-  std::vector<ColdSlot> cold_slots;
-  int E = 0, nb = 0, nr = 0, A = 0, T = 0, nmax = 0;
-  long long env_base = 0;
-  int G = 0, W16 = 0;
-  bool terrain = false;
-  // device buffers
-  uint8_t *d_grid = nullptr;
-  float *d_gridf = nullptr, *d_winf = nullptr, *d_dummy = nullptr;
-  unsigned long long *d_prof = nullptr;  // LNW_PROF phase timestamps
-  size_t prof_cap = 0;                   // d_prof capacity in slots (grown to the launch grid)
-  lnw_analytics ana{};                   // bound analytics buffers (lnw_set_analytics)
-  unsigned long long *ctr = nullptr;     // bound work counters (lnw_set_counters)
-  // diagnostics knobs, read once at lnw_create (LNW_DEBUG_SKIP / LNW_PROF / LNW_FORCE_GENERIC)
-  int dbg_skip = 0;
-  bool prof = false, force_generic = false, no_group = false, group_fits = false, no_units = false;
-  bool no_slab = false;  // LNW_NO_SLAB: no two-slab direct rows (A/B)
-  bool force_group = false;  // LNW_FORCE_GROUP (A/B): the group kernel for templated team sizes too
-  bool no_split_rows = false;  // LNW_NO_SPLIT_ROWS (A/B): row-writing contact steps keep phase S on one wave
-  bool store_wt = false;
-  bool units_fit = false;  // UNITS blocks of the step layout fit one workgroup (lnw_load_terrain)
-  bool contact = false;  // lnw_set_variant: contact-heavy phase-S code in the templated kernels
-  int last_kernel = LNW_KERNEL_NONE;     // lnw_step_kernel: what the last lnw_step launched
-  bool has_medium = false;               // the spawn spec has medium ships (runtime-size kernels only)
-  unsigned long long terrain_hash = 0;   // FNV-1a of the loaded grid (state snapshots name their terrain)
-  uint32_t *d_mask2 = nullptr, *d_mvtab = nullptr, *d_lostab = nullptr;
-  uint32_t *pos = nullptr;
-  int32_t *radar = nullptr, *steps = nullptr, *envi = nullptr;
-  uint8_t *miss = nullptr, *mkind = nullptr, *alive = nullptr, *type = nullptr;
-  double *dist_lz = nullptr, *duct = nullptr, *bear_val = nullptr, *d_atan = nullptr;
-  uint8_t *bear_ship = nullptr;
-  uint16_t *tl_cnt = nullptr, *tl = nullptr;
-  unsigned long long *rng = nullptr;
-  uint32_t *err = nullptr;
-  int32_t *sp_types = nullptr, *sp_pos = nullptr, *sp_randls = nullptr, *sp_pos_env = nullptr;
-  bool sp_pos_env_on = false;  // auto-reset respawns on the per-env cells of the last lnw_reset
-  const double *tape = nullptr;
-  const long long *tape_off = nullptr;
-  std::vector<void *> allocs;
-};
-
-namespace {
-
-template <class T>
-int dalloc(lnw_handle *h, T **p, size_t n) {
-  void *q = nullptr;
-  hipError_t e = hipMalloc(&q, n * sizeof(T) + 16);
-  if (e != hipSuccess) return fail(LNW_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-  (void)hipMemset(q, 0, n * sizeof(T) + 16);
-  h->allocs.push_back(q);
-  *p = (T *)q;
-  return 0;
-}
-
-KState make_state(lnw_handle *h) {
-  KState s{};
-  s.pos = h->pos; s.radar = h->radar; s.miss = h->miss; s.mkind = h->mkind; s.alive = h->alive;
-  s.type = h->type; s.steps = h->steps; s.dist_lz = h->dist_lz; s.tl_cnt = h->tl_cnt; s.tl = h->tl;
-  s.duct = h->duct; s.envi = h->envi; s.rng = h->rng; s.err = h->err;
-  s.atan_deg = h->d_atan;
-  s.grid = h->d_grid; s.gridf = h->d_gridf; s.winf = h->d_winf; s.dummy = h->d_dummy; s.prof = nullptr; s.cold = nullptr; s.mask2 = h->d_mask2; s.mvtab = h->d_mvtab; s.lostab = h->d_lostab;
-  s.nmax = h->nmax;
-  return s;
-}
-
-// The device block holding the handle's current cold values (KCold), for the
-// launch about to be made. Blocks are versioned, never rewritten: a set of
-// values not seen before gets a block of its own, written (a blocking copy)
-// before this returns, and launches made from now on point to it; launches
-// already queued, and captured graphs, keep reading the block they were given,
-// which stays as it was until lnw_destroy. So no setter has to wait for the
-// device, and a value set back to an earlier one (counters or analytics
-// toggled) reuses that block. Every entry point that launches a kernel taking KState goes
-// through here (launch_state), so whatever changed the handle (a setter,
-// lnw_reset's spawn spec, lnw_set_state) is picked up; the setters also commit
-// at once, so that a step captured into a graph right after them finds its
-// block ready (no allocation while capturing).
-int cold_commit(lnw_handle *h, ColdPtr *out) {
-  KCold c;
-  memset(&c, 0, sizeof c);
-  c.ana = h->ana;
-  c.tape = h->tape; c.tape_off = h->tape_off;
-  c.sp_types = h->sp_types; c.sp_pos = h->sp_pos; c.sp_randls = h->sp_randls;
-  c.sp_pos_env = h->sp_pos_env_on ? h->sp_pos_env : nullptr;
-  c.bear_val = h->bear_val; c.bear_ship = h->bear_ship;
-  c.ctr = h->ctr;
-  // newest first: the current block is almost always the last one made
-  for (size_t i = h->cold_slots.size(); i-- > 0;)
-    if (memcmp(&h->cold_slots[i].host, &c, sizeof c) == 0) {
-      if (out) *out = (ColdPtr)h->cold_slots[i].dev;
-      return 0;
-    }
-  KCold *d = nullptr;
-  HIPCHK(hipSetDevice(h->device));
-  if (int rc = dalloc(h, &d, 1)) return rc;
-  HIPCHK(hipMemcpy(d, &c, sizeof c, hipMemcpyHostToDevice));
-  h->cold_slots.push_back({c, d});
-  if (out) *out = (ColdPtr)d;
-  return 0;
-}
-
-// A launch's KState: the handle's arrays and the cold block's pointer.
-int launch_state(lnw_handle *h, KState &s) {
-  s = make_state(h);
-  return cold_commit(h, &s.cold);
-}
-
-size_t step_lds_bytes(const lnw_handle *h) {
-  LdsLayout L = lds_layout(h->A, h->nb, h->nr, h->nmax, h->G * h->W16, h->G);
-  return (size_t)L.total;
-}
-
-// the step launch's LDS: step_lds_bytes plus the whole-side row stages of
-// small quiet workgroups (the same condition step_kernel evaluates)
-// compute units of the handle's device (cached per device)
-int device_ncu(int dev) {
-  static int cache[64] = {0};
-  int &c = cache[dev & 63];
-  if (c == 0) {
-    int n = 0;
-    c = hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0 ? n : 256;
-  }
-  return c;
-}
-
-// Quiet workgroups' direct rows (quiet_step_t): a workgroup of up to 64 / nb envs
-// stages both sides' rows whole (qbig) and wave 1 builds and stores every row
-// from registers; up to 128 / nb envs it does so in two slabs of 64 / nb envs,
-// for the non-contact kernels and only when the larger LDS still holds the whole
-// grid at once (config 3 at N = 4: 16 384 envs, 32 per workgroup). Larger
-// workgroups stream their rows in staged passes (quiet_emit_t).
-bool step_qdirect(const lnw_handle *h, int epw) {
-  const bool tmpl = !h->force_generic && !h->has_medium && h->params.los_mode == 0 && h->nb == h->nr &&
-                    h->nb >= 2 && h->nb <= 4 && EPW == WAVE;
-  if (!tmpl) return false;
-  if (epw * h->nb <= WAVE) return true;
-  // (4v4 only: step_kernel<4, 4, .., SL> is the one two-slab instantiation)
-  if (h->nb != 4 || h->contact || h->no_slab || epw * h->nb > 2 * WAVE) return false;
-  const LdsLayout L = lds_layout(h->A, h->nb, h->nr, h->nmax, h->G * h->W16, h->G, WAVE);
-  int per_cu = (int)((160 * 1024) / ((size_t)L.total + 1024));
-  if (per_cu > 4) per_cu = 4;  // 256 VGPRs: two waves per SIMD
-  return (h->E + epw - 1) / epw <= (long long)device_ncu(h->device) * per_cu;
-}
-
-size_t step_launch_lds_bytes(const lnw_handle *h, int epw) {
-  const int rows = step_qdirect(h, epw) ? (epw * h->nb < WAVE ? epw * h->nb : WAVE) : 0;
-  LdsLayout L = lds_layout(h->A, h->nb, h->nr, h->nmax, h->G * h->W16, h->G, rows);
-  return (size_t)L.total;
-}
-
-// Environments per workgroup: EPW (one env per lane) unless that leaves the GPU
-// with fewer workgroups than it can hold at once; then halve it (down to 16 for
-// the two-wave kernels, 1 otherwise) until the grid fills every resident slot. A step is a per-lane latency chain, so a
-// workgroup with fewer live lanes takes about as long as a full one, and more
-// workgroups in flight finish the batch in fewer rounds (config 4: 8 192 envs
-// -> 512 workgroups of 16 instead of 128 of 64). LNW_EPW_RT overrides.
-int choose_epw(const lnw_handle *h) {
-  if (const char *e = getenv("LNW_EPW_RT")) {
-    int v = atoi(e);
-    if (v >= 1 && v <= EPW) return v;
-  }
-  int ncu = 256;
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, h->device) == hipSuccess && prop.multiProcessorCount > 0)
-    ncu = prop.multiProcessorCount;
-  const bool two_wave = !h->force_generic && h->params.los_mode != 2 && h->nb == h->nr && h->nb >= 2 && h->nb <= 4 && EPW == WAVE;
-  const int by_waves = two_wave ? 4 : 8;  // 256 VGPRs: two waves per SIMD
-  // resident workgroups at a given epw (the launch's LDS depends on it: small
-  // quiet workgroups carry whole-side row stages)
-  auto slots = [&](int e) {
-    const size_t lds = step_launch_lds_bytes(h, e) + 1024;
-    int per_cu = (int)((160 * 1024) / lds);
-    if (per_cu > by_waves) per_cu = by_waves;
-    if (per_cu < 1) per_cu = 1;
-    return (long long)ncu * per_cu;
-  };
-  // two-wave kernels stop at 16 envs per workgroup: below that each workgroup's
-  // fixed head (terrain mask staging, state columns) outweighs the shorter
-  // chain (8 192 envs: 20.2 us at 16, 20.5 at 8, 22.3 at 32, 29.0 at 64)
-  const int min_epw = two_wave ? 16 : 1;
-  int epw = EPW;
-  while (epw > min_epw && (h->E + epw - 1) / epw < slots(epw)) epw /= 2;
-  if ((h->E + epw - 1) / epw > slots(epw) && epw < EPW) epw *= 2;  // never more rounds than EPW needs
-  return epw;
-}
-
-}  // namespace
-
-// LNW_PROF diagnostics: mean per-workgroup phase spans and the grid-wide
-// start / end spread of one step launch (synchronises the stream).
-void prof_report(lnw_handle *h, hipStream_t st, int nwg) {
-  std::vector<unsigned long long> t((size_t)nwg * PROF_SLOTS);
-  if (hipMemcpyAsync(t.data(), h->d_prof, t.size() * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess)
-    return;
-  double sL = 0, sM = 0, sS = 0, sW = 0, s1 = 0, sa[8] = {0}, sq[4] = {0}, sp[4] = {0}, sg[4] = {0},
-         st3[3] = {0, 0, 0};
-  int nq = 0;
-  unsigned long long t0 = ~0ull, tend0 = 0, tend1 = 0;
-  int n1 = 0;
-  for (int w = 0; w < nwg; w++) {
-    const unsigned long long *r = &t[(size_t)w * PROF_SLOTS];
-    sL += (double)(r[4] - r[0]);
-    sM += (double)(r[1] - r[4]);
-    sS += (double)(r[2] - r[1]);
-    sW += (double)(r[3] - r[2]);
-    if (r[5]) { s1 += (double)(r[5] - r[0]); n1++; if (r[5] > tend1) tend1 = r[5]; }
-    for (int q = 0; q < 4; q++) sp[q] += (double)r[16 + q];
-    for (int q = 0; q < 4; q++) sg[q] += (double)r[20 + q];
-    if (r[14]) {  // quiet workgroup: M end | A* + barrier | predicate | phase Q + barrier
-      nq++;
-      sq[0] += (double)(r[6] - r[4]);
-      sq[1] += (double)(r[7] - r[6]);
-      sq[2] += (double)(r[8] - r[7]);
-      sq[3] += (double)(r[9] - r[8]);
-      if (r[10] && r[11]) {  // tail: rewards | cog | env_tail + outputs
-        st3[0] += (double)(r[10] - r[1]);
-        st3[1] += (double)(r[11] - r[10]);
-        st3[2] += (double)(r[2] - r[11]);
-      }
-    } else {
-      for (int a = 0; a < 8; a++)
-        if (r[6 + a]) sa[a] += (double)(r[6 + a] - (a ? r[5 + a] : r[1]));
-    }
-    if (r[0] < t0) t0 = r[0];
-    if (r[3] > tend0) tend0 = r[3];
-  }
-  const double us = 0.01;  // 100 MHz ticks
-  {  // spread of the per-workgroup phase-S spans (slot 1 -> 2)
-    std::vector<double> sv;
-    for (int w = 0; w < nwg; w++) {
-      const unsigned long long *r = &t[(size_t)w * PROF_SLOTS];
-      if (r[2] > r[1]) sv.push_back((double)(r[2] - r[1]) * 0.01);
-    }
-    {  // the slowest workgroup's parts (slots 16..23)
-      int wm = -1;
-      double best = -1;
-      for (int w = 0; w < nwg; w++) {
-        const unsigned long long *r = &t[(size_t)w * PROF_SLOTS];
-        if (r[2] > r[1] && (double)(r[2] - r[1]) > best) { best = (double)(r[2] - r[1]); wm = w; }
-      }
-      if (wm >= 0) {
-        const unsigned long long *r = &t[(size_t)wm * PROF_SLOTS];
-        fprintf(stderr, "[lnw prof] slowest workgroup %d: S %.1f us = take_action %.1f, LOS prefetch %.1f, get_obs %.1f "
-                        "(walk %.1f, observed %.1f, bearings %.1f, fix targets %.1f), reward %.1f\n",
-                wm, best * 0.01, r[16] * 0.01, r[17] * 0.01, r[18] * 0.01, r[20] * 0.01, r[21] * 0.01,
-                r[22] * 0.01, r[23] * 0.01, r[19] * 0.01);
-      }
-    }
-    std::sort(sv.begin(), sv.end());
-    if (!sv.empty())
-      fprintf(stderr, "[lnw prof] phase S span per workgroup: p10 %.1f, p50 %.1f, p90 %.1f, max %.1f us\n",
-              sv[sv.size() / 10], sv[sv.size() / 2], sv[sv.size() * 9 / 10], sv.back());
-  }
-  fprintf(stderr, "[lnw prof] wg=%d mean L %.2f us, M %.2f us, S %.2f us, W %.2f us, wave1 end-from-start %.2f us; "
-                  "grid: last wave0 end %.2f us, last wave1 end %.2f us after first start\n",
-          nwg, sL / nwg * us, sM / nwg * us, sS / nwg * us, sW / nwg * us, n1 ? s1 / n1 * us : 0.0,
-          (double)(tend0 - t0) * us, tend1 ? (double)(tend1 - t0) * us : 0.0);
-  {
-    double bs = 0, bm = 0, bl = 0;
-    for (int w = 0; w < nwg; w++) {
-      const unsigned long long *r = &t[(size_t)w * PROF_SLOTS];
-      bs += (double)r[24]; bm += (double)r[25]; bl += (double)r[26];
-    }
-    if (bl > 0)
-      fprintf(stderr, "[lnw prof] EW bearings (contact variant): %.0f evaluated, wave max summed %.0f, "
-                      "active lanes %.0f; balanced/actual %.3f\n",
-              bs, bm, bl, bs / 64.0 / bm);
-  }
-  {  // grid timeline: workgroup start (slot 0), stream / phase S start (slot 1),
-     // wave-1 end (slot 5), each as p10 / p50 / p90 / max after the first start
-    const int slots[3] = {0, 1, 5};
-    const char *names[3] = {"start", "S/stream start", "wave-1 end"};
-    for (int k = 0; k < 3; k++) {
-      std::vector<double> sv;
-      for (int w = 0; w < nwg; w++) {
-        const unsigned long long v = t[(size_t)w * PROF_SLOTS + slots[k]];
-        if (v >= t0) sv.push_back((double)(v - t0) * us);
-      }
-      std::sort(sv.begin(), sv.end());
-      if (!sv.empty())
-        fprintf(stderr, "[lnw prof] timeline %s: p10 %.2f, p50 %.2f, p90 %.2f, max %.2f us\n", names[k],
-                sv[sv.size() / 10], sv[sv.size() / 2], sv[sv.size() * 9 / 10], sv.back());
-    }
-  }
-  {  // wave-1 end (slot 5) per XCC: count, mean, max after the first start
-    double se[16] = {0}, mx[16] = {0};
-    int nx[16] = {0};
-    for (int w = 0; w < nwg; w++) {
-      const unsigned long long *r = &t[(size_t)w * PROF_SLOTS];
-      if (!r[5] || r[5] < t0) continue;
-      const int x = (int)(r[30] & 15);
-      const double e = (double)(r[5] - t0) * us;
-      se[x] += e; nx[x]++;
-      if (e > mx[x]) mx[x] = e;
-    }
-    {  // per CU (XCC, SE, SH, CU from HW_ID bits 15:8): spread of CU means vs within-CU spread
-      std::vector<std::pair<int, double>> v;
-      for (int w = 0; w < nwg; w++) {
-        const unsigned long long *r = &t[(size_t)w * PROF_SLOTS];
-        if (!r[5] || r[5] < t0) continue;
-        v.push_back({(int)((r[30] & 15) << 8 | ((r[31] >> 8) & 0xff)), (double)(r[5] - t0) * us});
-      }
-      std::sort(v.begin(), v.end());
-      std::vector<double> means, spans;
-      for (size_t i = 0; i < v.size();) {
-        size_t j = i;
-        double sm = 0, lo = 1e30, hi = -1e30;
-        while (j < v.size() && v[j].first == v[i].first) { sm += v[j].second; lo = std::min(lo, v[j].second); hi = std::max(hi, v[j].second); j++; }
-        means.push_back(sm / (double)(j - i));
-        spans.push_back(hi - lo);
-        i = j;
-      }
-      std::sort(means.begin(), means.end());
-      std::sort(spans.begin(), spans.end());
-      if (!means.empty())
-        fprintf(stderr, "[lnw prof] CUs %zu: CU-mean wave-1 end p10 %.1f p50 %.1f p90 %.1f max %.1f; within-CU span p50 %.1f p90 %.1f max %.1f us\n",
-                means.size(), means[means.size() / 10], means[means.size() / 2], means[means.size() * 9 / 10], means.back(),
-                spans[spans.size() / 2], spans[spans.size() * 9 / 10], spans.back());
-    }
-    {  // SIMD placement: wave 0 (phase S) sharing its SIMD with another workgroup's wave 0
-      std::vector<int> key(nwg);
-      for (int w = 0; w < nwg; w++) {
-        const unsigned long long *r = &t[(size_t)w * PROF_SLOTS];
-        key[w] = (int)((r[30] & 15) << 12 | ((r[31] >> 8) & 0xff) << 4 | ((r[31] >> 4) & 3));
-      }
-      std::vector<int> sk = key;
-      std::sort(sk.begin(), sk.end());
-      double e0[2] = {0, 0}, m0[2] = {0, 0};
-      int n0[2] = {0, 0}, same = 0;
-      for (int w = 0; w < nwg; w++) {
-        const unsigned long long *r = &t[(size_t)w * PROF_SLOTS];
-        const int cnt = (int)(std::upper_bound(sk.begin(), sk.end(), key[w]) - std::lower_bound(sk.begin(), sk.end(), key[w]));
-        const int k = cnt > 1 ? 1 : 0;
-        if (r[3] < t0) continue;
-        const double e = (double)(r[3] - t0) * us;
-        e0[k] += e; n0[k]++;
-        if (e > m0[k]) m0[k] = e;
-        same += ((r[31] >> 4) & 3) == ((r[29] >> 4) & 3);
-      }
-      fprintf(stderr, "[lnw prof] wave-0 SIMD: alone %d (end mean %.1f max %.1f us), shared %d (mean %.1f max %.1f us); "
-                      "waves 0/1 on one SIMD in %d workgroups\n",
-              n0[0], n0[0] ? e0[0] / n0[0] : 0.0, m0[0], n0[1], n0[1] ? e0[1] / n0[1] : 0.0, m0[1], same);
-    }
-    fprintf(stderr, "[lnw prof] wave-1 end by XCC (n/mean/max us):");
-    for (int x = 0; x < 16; x++)
-      if (nx[x]) fprintf(stderr, " %d:%d/%.1f/%.1f", x, nx[x], se[x] / nx[x], mx[x]);
-    fprintf(stderr, "; block%%8==xcc for %d of %d\n",
-            [&] { int k = 0; for (int w = 0; w < nwg; w++) k += (int)(t[(size_t)w * PROF_SLOTS + 30] & 15) == (w & 7); return k; }(), nwg);
-  }
-  {
-    double rq = 0;
-    int nr2 = 0;
-    for (int w = 0; w < nwg; w++) {
-      const unsigned long long *r = &t[(size_t)w * PROF_SLOTS];
-      if (r[14] && r[12] > r[8] && r[8]) { rq += (double)(r[12] - r[8]); nr2++; }
-    }
-    if (nr2) fprintf(stderr, "[lnw prof] repeated quiet test (diagnostics): %.2f us\n", rq / nr2 * us);
-  }
-  {  // quiet small workgroups (direct mode): each wave's phase-Q work from the
-     // test's end (slots 27 / 15), wave 1's rows staged (28) and stored (5)
-     // from the barrier (9)
-    double q0 = 0, q1 = 0, rb = 0, rc = 0;
-    int nd = 0;
-    for (int w = 0; w < nwg; w++) {
-      const unsigned long long *r = &t[(size_t)w * PROF_SLOTS];
-      if (!r[14] || !r[28] || !r[15] || !r[27] || r[28] < r[9]) continue;
-      nd++;
-      q0 += (double)(r[27] - r[8]);
-      q1 += (double)(r[15] - r[8]);
-      rb += (double)(r[28] - r[9]);
-      rc += (double)(r[5] - r[28]);
-    }
-    if (nd)
-      fprintf(stderr, "[lnw prof] quiet direct %d: phase-Q work wave 0 %.2f, wave 1 %.2f us; after the barrier "
-                      "rows staged %.2f, stored %.2f us\n",
-              nd, q0 / nd * us, q1 / nd * us, rb / nd * us, rc / nd * us);
-  }
-#ifdef LNW_DIAG
-  {  // quiet workgroups: the kernel's first instruction (slot 13) to stamp 0, and stamp 0 to phase L's end
-    double se = 0, sl = 0, me = 0;
-    int ne = 0;
-    for (int w = 0; w < nwg; w++) {
-      const unsigned long long *r = &t[(size_t)w * PROF_SLOTS];
-      if (!r[14] || !r[13] || r[13] > r[0]) continue;
-      ne++;
-      se += (double)(r[0] - r[13]);
-      sl += (double)(r[4] - r[0]);
-      if ((double)(r[0] - r[13]) > me) me = (double)(r[0] - r[13]);
-    }
-    if (ne)
-      fprintf(stderr, "[lnw prof] entry -> stamp 0 %.3f us (max %.2f), stamp 0 -> phase-L end %.3f us (%d quiet records)\n",
-              se / ne * us, me * us, sl / ne * us, ne);
-  }
-#endif
-  if (nq)
-    fprintf(stderr, "[lnw prof] quiet workgroups %d: M %.2f us, A*+barrier %.2f us, quiet test %.2f us, Q+barrier %.2f us; "
-                    "tail: rewards %.2f, cog %.2f, env_tail+outputs %.2f us\n",
-            nq, sq[0] / nq * us, sq[1] / nq * us, sq[2] / nq * us, sq[3] / nq * us, st3[0] / nq * us,
-            st3[1] / nq * us, st3[2] / nq * us);
-  const int ns = nwg - nq;
-  fprintf(stderr, "[lnw prof] phase S workgroups %d, per agent (us):", ns);
-  for (int a = 0; a < 8; a++) fprintf(stderr, " %.2f", ns ? sa[a] / ns * us : 0.0);
-  fprintf(stderr, "; section totals take_action %.2f, LOS prefetch %.2f, get_obs %.2f, reward %.2f us\n",
-          ns ? sp[0] / ns * us : 0.0, ns ? sp[1] / ns * us : 0.0, ns ? sp[2] / ns * us : 0.0,
-          ns ? sp[3] / ns * us : 0.0);
-  fprintf(stderr, "[lnw prof] get_obs parts (templated): pair walk %.2f, observed stores %.2f, bearings+fixes %.2f, fix targets %.2f us\n",
-          ns ? sg[0] / ns * us : 0.0, ns ? sg[1] / ns * us : 0.0, ns ? sg[2] / ns * us : 0.0,
-          ns ? sg[3] / ns * us : 0.0);
-}
-
-extern "C" {
-
-int lnw_abi_version(void) { return LNW_ABI_VERSION; }
-const char *lnw_last_error(void) { return g_err.c_str(); }
-
-int lnw_set_analytics(lnw_handle *h, const lnw_analytics *a) {
-  if (!h) return fail(LNW_EINVAL, "null handle");
-  if (!a) { h->ana = lnw_analytics{}; return cold_commit(h, nullptr); }
-  if ((a->eng_log && (!a->eng_count || a->eng_cap < 0)) || (a->ew_log && (!a->ew_count || a->ew_cap < 0)))
-    return fail(LNW_EINVAL, "analytics log without a counter or with a negative capacity");
-  h->ana = *a;
-  return cold_commit(h, nullptr);
-}
-
-int lnw_hit_tables(double *tab64, float *tab32) {
-  KParams k{};
-  host_constants(k);
-  for (int h = 0; h < 2; h++)
-    for (int n = 0; n < 9; n++) {
-      if (tab64) tab64[h * 9 + n] = k.hit64[h][n];
-      if (tab32) tab32[h * 9 + n] = k.hit32[h][n];
-    }
-  return 0;
-}
-
-int lnw_create(const lnw_params *params, int32_t n_envs, int32_t nb, int32_t nr, int32_t device,
-               int64_t env_id_base, lnw_handle **out) {
-  if (!params || !out) return fail(LNW_EINVAL, "null argument");
-  if (n_envs <= 0) return fail(LNW_EINVAL, "n_envs must be > 0");
-  if (nb < 1 || nr < 1 || nb > 16 || nr > 16)
-    return fail(LNW_EUNSUPPORTED, "need 1 <= nb, nr <= 16 ships per side");
-  HIPCHK(hipSetDevice(device));
-  lnw_handle *h = new lnw_handle();
-  h->device = device;
-  if (const char *dbg = getenv("LNW_DEBUG_SKIP")) h->dbg_skip = atoi(dbg);
-#ifndef LNW_DIAG
-  // the shipped library honours only the knobs that change the launch shape or
-  // code path, never the results (bit 9: no quiet path, 15: the group kernel's
-  // fire loop entry by entry, 17: per-lane bearing loop, 22/23: where the
-  // head's loads are issued, 28: the per-env quiet test in small workgroups,
-  // 29: their env counters loaded in phase Q); section skips and
-  // replaced arithmetic exist only in the diagnostics build (-DLNW_DIAG,
-  // lnw.build.build_diag)
-  constexpr int kResultPreserving = 512 | 32768 | 131072 | 4194304 | 8388608 | (1 << 28) | (1 << 29);
-  if (h->dbg_skip & ~kResultPreserving) {
-    const int bad = h->dbg_skip & ~kResultPreserving;
-    delete h;
-    return fail(LNW_EINVAL, "LNW_DEBUG_SKIP bits " + std::to_string(bad) +
-                                " change results; they exist only in the diagnostics build (-DLNW_DIAG)");
-  }
-#endif
-  h->prof = getenv("LNW_PROF") != nullptr;
-  h->force_generic = getenv("LNW_FORCE_GENERIC") != nullptr;
-  // LNW_NO_GROUP: runtime team sizes on the one-lane-per-env kernel (A/B tests)
-  h->no_group = getenv("LNW_NO_GROUP") != nullptr;
-  h->force_group = getenv("LNW_FORCE_GROUP") != nullptr;
-  h->no_split_rows = getenv("LNW_NO_SPLIT_ROWS") != nullptr;
-  // LNW_NO_UNITS: one 64-env unit per workgroup for the headline shape (A/B tests)
-  h->no_units = getenv("LNW_NO_UNITS") != nullptr;
-  h->no_slab = getenv("LNW_NO_SLAB") != nullptr;
-  h->kp.xcd_remap = getenv("LNW_NO_XCD_REMAP") == nullptr ? 1 : 0;
-  // LNW_GROUP_MARCH=1: the group kernel marches its pair LOS over the LDS
-  // terrain mask instead of loading LOS-table words (A/B)
-  h->kp.group_march = getenv("LNW_GROUP_MARCH") != nullptr ? 1 : 0;
-  // write-through observation stores (st_obs4) while a side's output fits the
-  // 32-bit buffer offsets; LNW_NO_STORE_WT keeps non-temporal stores (A/B)
-  {
-    const int ns = nb > nr ? nb : nr;
-    const double side_bytes = (double)n_envs * ns * (4 * ns + 52) * 4.0;
-    h->store_wt = getenv("LNW_NO_STORE_WT") == nullptr && side_bytes < 2147483648.0;
-  }
-  h->params = *params;
-  h->E = n_envs; h->nb = nb; h->nr = nr; h->A = nb + nr;
-  h->nmax = nb > nr ? nb : nr;
-  h->T = h->nmax + h->nmax * h->nmax;
-  h->env_base = env_id_base;
-  const size_t E = (size_t)n_envs, A = (size_t)h->A;
-  int rc = 0;
-  rc |= dalloc(h, &h->pos, A * E);
-  rc |= dalloc(h, &h->radar, A * E);
-  rc |= dalloc(h, &h->miss, A * E);
-  rc |= dalloc(h, &h->mkind, A * E);
-  rc |= dalloc(h, &h->alive, A * E);
-  rc |= dalloc(h, &h->type, A * E);
-  rc |= dalloc(h, &h->steps, A * E);
-  rc |= dalloc(h, &h->dist_lz, A * E);
-  rc |= dalloc(h, &h->tl_cnt, A * E);
-  rc |= dalloc(h, &h->tl, A * (size_t)h->T * E);
-  rc |= dalloc(h, &h->duct, E);
-  rc |= dalloc(h, &h->envi, 8 * E);
-  rc |= dalloc(h, &h->rng, E);
-  rc |= dalloc(h, &h->err, E);
-  rc |= dalloc(h, &h->bear_val, (size_t)h->nmax * h->nmax * E);
-  rc |= dalloc(h, &h->bear_ship, (size_t)h->nmax * h->nmax * E);
-  rc |= dalloc(h, &h->sp_types, 64);
-  rc |= dalloc(h, &h->sp_pos, 128);
-  rc |= dalloc(h, &h->sp_randls, 64);
-  rc |= dalloc(h, &h->d_dummy, 4 * 64);
-  rc |= dalloc(h, &h->d_atan, (size_t)LOS_W * LOS_W);
-  if (rc) {
-    std::string m = g_err;
-    lnw_destroy(h);
-    return fail(LNW_ENOMEM, m);
-  }
-  {  // EW bearing table: math.degrees(math.atan2(dy, dx)) for integer offsets in
-     // [-R_LOS, R_LOS]^2, computed by the host libm as the reference does
-     // (combatant.py:253), so the device needs no atan2 of its own in range
-    std::vector<double> at((size_t)LOS_W * LOS_W);
-    for (int dy = -R_LOS; dy <= R_LOS; dy++)
-      for (int dx = -R_LOS; dx <= R_LOS; dx++)
-        at[(size_t)(dy + R_LOS) * LOS_W + (dx + R_LOS)] = atan2((double)dy, (double)dx) * (180.0 / PY_PI);
-    HIPCHK(hipMemcpy(h->d_atan, at.data(), at.size() * sizeof(double), hipMemcpyHostToDevice));
-    // odd in dy (glibc's atan2 is; checked, not assumed): the group kernel then
-    // keeps only the dy >= 0 rows in LDS and negates for dy < 0
-    bool odd = true;
-    for (int dy = 1; dy <= R_LOS; dy++)
-      for (int dx = -R_LOS; dx <= R_LOS; dx++)
-        odd = odd && at[(size_t)(R_LOS - dy) * LOS_W + (dx + R_LOS)] == -at[(size_t)(R_LOS + dy) * LOS_W + (dx + R_LOS)];
-    h->kp.atan_odd = odd ? 1 : 0;
-  }
-  KParams &k = h->kp;
-  k.discrete = params->discrete; k.landing_ops = params->landing_ops;
-  k.aggressive = params->aggressive; k.side_blue = params->side_blue;
-  k.trained_red = params->trained_red; k.move_thr = params->move_thr; k.ew_thr = params->ew_thr;
-  k.lz_x = params->lz_x; k.lz_y = params->lz_y; k.red_aggression = params->red_aggression;
-  k.episode_steps = params->episode_steps; k.auto_reset = params->auto_reset;
-  k.los_mode = params->los_mode; k.move_mode = params->move_mode;
-  k.E = n_envs; k.nb = nb; k.nr = nr; k.A = h->A; k.T = h->T;
-  k.env_base = env_id_base;
-  k.rng_mode = LNW_RNG_PHILOX;
-  k.seed = 0;
-  k.epw = EPW;  // refined by lnw_load_terrain (choose_epw) once the LDS size is known
-  k.wc[0] = k.wc[1] = 49;  // 7x7 windows until a reset spawns a side of medium ships
-  host_constants(k);
-  *out = h;
-  return 0;
-}
-
-int lnw_destroy(lnw_handle *h) {
-  if (!h) return 0;
-  (void)hipSetDevice(h->device);
-  (void)hipDeviceSynchronize();
-  for (void *p : h->allocs) (void)hipFree(p);
-  if (h->d_prof) (void)hipFree(h->d_prof);
-  delete h;
-  return 0;
-}
-
-int lnw_load_terrain(lnw_handle *h, const uint8_t *grid_host, int32_t G) {
-  if (!h || !grid_host) return fail(LNW_EINVAL, "null argument");
-  if (G < 8 || G > 1024) return fail(LNW_EINVAL, "grid size out of range");
-  HIPCHK(hipSetDevice(h->device));
-  h->G = G;
-  h->W16 = (G + 15) / 16;
-  int rc = 0;
-  if (h->d_grid) {  // re-load: release the previous terrain structures
-    HIPCHK(hipDeviceSynchronize());
-    void *old[6] = {h->d_grid, h->d_gridf, h->d_winf, h->d_mask2, h->d_mvtab, h->d_lostab};
-    for (void *p : old) {
-      for (size_t i = 0; i < h->allocs.size(); i++)
-        if (h->allocs[i] == p) { (void)hipFree(p); h->allocs.erase(h->allocs.begin() + i); break; }
-    }
-  }
-  rc |= dalloc(h, &h->d_grid, (size_t)G * G);
-  rc |= dalloc(h, &h->d_gridf, (size_t)G * G);
-  rc |= dalloc(h, &h->d_winf, (size_t)3 * G * G * 52);
-  rc |= dalloc(h, &h->d_mask2, (size_t)G * h->W16);
-  rc |= dalloc(h, &h->d_mvtab, (size_t)MV_CLASSES * G * G * MV_WORDS);
-  rc |= dalloc(h, &h->d_lostab, (size_t)G * G * LOS_CELL_WORDS);
-  if (rc) return rc;
-  HIPCHK(hipMemcpy(h->d_grid, grid_host, (size_t)G * G, hipMemcpyHostToDevice));
-  {
-    unsigned long long fh = 1469598103934665603ull ^ (unsigned long long)G;
-    for (size_t i = 0; i < (size_t)G * G; i++) fh = (fh ^ grid_host[i]) * 1099511628211ull;
-    h->terrain_hash = fh;
-  }
-  {  // observation window values grid/255 (combatant.py:177), float64 quotient -> float32
-    std::vector<float> gf((size_t)G * G);
-    for (size_t i = 0; i < gf.size(); i++) gf[i] = (float)((double)grid_host[i] / 255.0);
-    HIPCHK(hipMemcpy(h->d_gridf, gf.data(), gf.size() * sizeof(float), hipMemcpyHostToDevice));
-    // per-cell observation windows, one 52-float (13 x float4) record per cell
-    // and class: [0] Combatant 7x7 around the ship (49 floats), [1] LandingShip
-    // 5x5 rows/cols pos-1..pos+3 (25 floats), [2] medium Combatant 5x5 around
-    // the ship (speed 2: combatant.py:165-181); cells outside the hard-coded
-    // 0..99 are 0 (combatant.py:176, landingship.py:183)
-    std::vector<float> wf((size_t)3 * G * G * 52, 0.0f);
-    auto cellv = [&](int x, int y) {
-      return (0 <= x && x < 100 && 0 <= y && y < 100 && x < G && y < G) ? gf[(size_t)x * G + y] : 0.0f;
-    };
-    for (int x = 0; x < G; x++)
-      for (int y = 0; y < G; y++) {
-        float *w7 = &wf[((size_t)x * G + y) * 52];
-        for (int i = 0; i < 7; i++)
-          for (int j = 0; j < 7; j++) w7[i * 7 + j] = cellv(x - 3 + i, y - 3 + j);
-        float *w5 = &wf[((size_t)G * G + (size_t)x * G + y) * 52];
-        for (int i = 0; i < 5; i++)
-          for (int j = 0; j < 5; j++) w5[i * 5 + j] = cellv(x - 1 + i, y - 1 + j);
-        float *wm = &wf[((size_t)2 * G * G + (size_t)x * G + y) * 52];
-        for (int i = 0; i < 5; i++)
-          for (int j = 0; j < 5; j++) wm[i * 5 + j] = cellv(x - 2 + i, y - 2 + j);
-      }
-    HIPCHK(hipMemcpy(h->d_winf, wf.data(), wf.size() * sizeof(float), hipMemcpyHostToDevice));
-  }
-  KParams &k = h->kp;
-  k.G = G;
-  k.W16 = h->W16;
-  int n = G * h->W16;
-  build_mask_kernel<<<(n + 255) / 256, 256>>>(h->d_grid, G, h->W16, k.move_thr, k.ew_thr, h->d_mask2);
-  HIPCHK(hipGetLastError());
-  long long nm = (long long)MV_CLASSES * G * G * MV_W * MV_W;
-  build_move_table_kernel<<<(unsigned)((nm + WAVE - 1) / WAVE), WAVE>>>(h->d_mask2, G, h->W16, h->d_mvtab);
-  HIPCHK(hipGetLastError());
-  long long nl = (long long)G * G * LOS_W;
-  const int mwords = G * h->W16 * 4 <= 64 * 1024 ? G * h->W16 : 0;  // terrain mask staged in LDS
-  {  // a few resident rounds of workgroups, each looping over its items
-    int ncu = 256;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, h->device) == hipSuccess && prop.multiProcessorCount > 0)
-      ncu = prop.multiProcessorCount;
-    const long long need = (nl + 255) / 256, cap = (long long)ncu * 8;
-    build_los_table_kernel<<<(unsigned)(need < cap ? need : cap), 256, (size_t)mwords * 4>>>(
-        h->d_mask2, G, h->W16, h->d_lostab, mwords);
-  }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipDeviceSynchronize());
-  h->terrain = true;
-  // dynamic LDS above the 64 KiB default needs an explicit opt-in
-  {
-    // the largest step launch (64 / nb envs per workgroup: the biggest row stages)
-    const size_t need = step_launch_lds_bytes(h, WAVE / h->nb);
-    // the same bound the launch attribute below grants
-    if (need > (size_t)GROUP_LDS_MAX) return fail(LNW_EUNSUPPORTED, "agent count needs more LDS than a CU has");
-    const LdsLayout GLy = lds_layout(h->A, h->nb, h->nr, h->nmax, h->G * h->W16, h->G);
-    const size_t gneed = (size_t)group_lds(GLy, h->G * h->W16, h->A, h->nb * h->nr, h->kp.atan_odd != 0).total + 1024;
-    // (else runtime sizes stay on step_kernel<0, 0>)
-    h->group_fits = group_lds(GLy, h->G * h->W16, h->A, h->nb * h->nr, h->kp.atan_odd != 0).ms >= 0;
-    // the limit is per kernel function and device, shared by every handle of
-    // the process on that device: set to GROUP_LDS_MAX once per device, so a
-    // smaller handle never lowers it under a larger one's launch (the launch's
-    // own size sets the occupancy); hipSetDevice(h->device) above selects it
-    static unsigned long long lds_opt_in = 0;  // bit d: device d done
-    const unsigned long long dbit = 1ull << (h->device & 63);
-    const size_t uneed = (size_t)UNITS * ((step_lds_bytes(h) + 15) & ~(size_t)15);
-    h->units_fit = uneed <= (size_t)UNITS_LDS_MAX;
-    if (!(lds_opt_in & dbit) && (need > 64 * 1024 || gneed > 64 * 1024 || uneed > 64 * 1024)) {
-      HIPCHK(hipFuncSetAttribute((const void *)step_kernel<4, 4, false, false, 1, false, true>,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, GROUP_LDS_MAX));
-      const void *ks[17] = {(const void *)step_kernel<4, 4, true, false, 1, true>,
-                            (const void *)step_kernel<0, 0>,       (const void *)step_kernel<2, 2>,
-                            (const void *)step_kernel<3, 3>,       (const void *)step_kernel<4, 4>,
-                            (const void *)step_kernel<2, 2, true>, (const void *)step_kernel<3, 3, true>,
-                            (const void *)step_kernel<4, 4, true>, (const void *)step_kernel<0, 0, false, true>,
-                            (const void *)observe_kernel<0, 0, false>, (const void *)step_group_kernel,
-                            (const void *)observe_kernel<2, 2, false>, (const void *)observe_kernel<3, 3, false>,
-                            (const void *)observe_kernel<4, 4, false>, (const void *)observe_kernel<2, 2, true>,
-                            (const void *)observe_kernel<3, 3, true>, (const void *)observe_kernel<4, 4, true>};
-      for (const void *kk : ks)
-        HIPCHK(hipFuncSetAttribute(kk, hipFuncAttributeMaxDynamicSharedMemorySize, GROUP_LDS_MAX));
-      HIPCHK(hipFuncSetAttribute((const void *)step_kernel<4, 4, false, false, UNITS>,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, UNITS_LDS_MAX));
-      lds_opt_in |= dbit;
-    }
-  }
-  (void)hipGetLastError();
-  h->kp.epw = choose_epw(h);
-  return 0;
-}
-
-int lnw_set_rng(lnw_handle *h, int32_t mode, uint64_t seed, const double *tape_dev,
-                const int64_t *tape_off_dev) {
-  if (!h) return fail(LNW_EINVAL, "null handle");
-  if (mode != LNW_RNG_PHILOX && mode != LNW_RNG_TAPE) return fail(LNW_EINVAL, "bad rng mode");
-  if (mode == LNW_RNG_TAPE && (!tape_dev || !tape_off_dev))
-    return fail(LNW_EINVAL, "tape mode needs tape and offsets");
-  HIPCHK(hipSetDevice(h->device));
-  h->kp.rng_mode = mode;
-  h->kp.seed = seed;
-  h->tape = tape_dev;
-  h->tape_off = (const long long *)tape_off_dev;
-  HIPCHK(hipMemset(h->rng, 0, sizeof(unsigned long long) * h->E));
-  return cold_commit(h, nullptr);
-}
-
-// Validate a spawn spec's ship types (blue then red) and derive what the
-// kernels key on: each side's window cells (wc) and whether the runtime-size
-// kernels must run (has_medium). Shared by lnw_reset and lnw_set_state, so a
-// snapshot restored into any handle selects the same kernels and row lengths
-// as the handle it was taken from. apply = false only validates.
-static int apply_side_types(lnw_handle *h, const int32_t *types, bool apply) {
-  int nmed[2] = {0, 0};
-  for (int a = 0; a < h->A; a++) {
-    const int t = types[a];
-    if (t != LNW_SMALL && t != LNW_LARGE && t != LNW_LS && t != LNW_MEDIUM)
-      return fail(LNW_EUNSUPPORTED, "ship type must be small, large, ls or medium");
-    if (t == LNW_MEDIUM) nmed[a >= h->nb]++;
-    if (h->params.discrete && t == LNW_LS)
-      return fail(LNW_EUNSUPPORTED, "LandingShip has no value_to_coordinates (DISCRETE mode)");
-  }
-  // a side's row length follows its fastest ship (game.py:595-610), and a
-  // medium ship's get_obs row has a 5x5 window (combatant.py:165-181): a side
-  // of medium ships only has 4 n + 28-float rows; medium ships beside speed-3
-  // ships make the reference's row assignment raise (game.py:344, 381)
-  for (int sd = 0; sd < 2; sd++) {
-    const int ns = sd ? h->nr : h->nb;
-    if (nmed[sd] && nmed[sd] != ns)
-      return fail(LNW_EUNSUPPORTED, "medium ships need a side of medium ships only (the reference's "
-                                    "rows are sized by the fastest ship, game.py:595-610)");
-  }
-  if (apply) {
-    h->kp.wc[0] = nmed[0] ? 25 : 49;
-    h->kp.wc[1] = nmed[1] ? 25 : 49;
-    h->has_medium = nmed[0] || nmed[1];
-  }
-  return 0;
-}
-
-int lnw_reset(lnw_handle *h, const uint8_t *env_mask_dev, const lnw_spawn *spawn,
-              const int32_t *pos_dev, void *stream) {
-  if (!h || !spawn) return fail(LNW_EINVAL, "null argument");
-  if (!h->terrain) return fail(LNW_ESTATE, "lnw_load_terrain must be called first");
-  HIPCHK(hipSetDevice(h->device));
-  if (int rc = apply_side_types(h, spawn->types, false)) return rc;
-  for (int a = 0; a < h->A; a++)
-    if (!spawn->rand_ls[a] && (spawn->pos[a][0] < 0 || spawn->pos[a][0] >= h->G ||
-                               spawn->pos[a][1] < 0 || spawn->pos[a][1] >= h->G))
-      return fail(LNW_EINVAL, "spawn position outside the grid");
-  apply_side_types(h, spawn->types, true);
-  hipStream_t st = (hipStream_t)stream;
-  HIPCHK(hipMemcpy(h->sp_types, spawn->types, sizeof(int32_t) * h->A, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(h->sp_pos, spawn->pos, sizeof(int32_t) * 2 * h->A, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(h->sp_randls, spawn->rand_ls, sizeof(int32_t) * h->A, hipMemcpyHostToDevice));
-  h->kp.box_lo[0] = spawn->box_lo[0]; h->kp.box_lo[1] = spawn->box_lo[1];
-  h->kp.box_hi[0] = spawn->box_hi[0]; h->kp.box_hi[1] = spawn->box_hi[1];
-  // per-env spawn cells: kept in the handle for the in-kernel auto-reset
-  if (pos_dev) {
-    const size_t n = (size_t)h->E * h->A * 2;
-    if (!h->sp_pos_env && dalloc(h, &h->sp_pos_env, n)) return LNW_ENOMEM;
-    HIPCHK(hipMemcpyAsync(h->sp_pos_env, pos_dev, n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-  }
-  h->sp_pos_env_on = pos_dev != nullptr;
-  KState s;
-  if (int rc = launch_state(h, s)) return rc;
-  reset_kernel<<<(h->E + 255) / 256, 256, 0, st>>>(h->kp, s, env_mask_dev);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-namespace {
-// lnw_step's launch (lnw_step_seq makes one per step)
-int step_launch(lnw_handle *h, void *actions_dev, int32_t action_dtype,
-                const uint8_t *row_kind_dev, float *obs_blue_dev, float *obs_red_dev, float *rew_blue_dev,
-                float *rew_red_dev, int32_t *done_dev, float *cog_dev, void *stream) {
-  if (!h || !actions_dev) return fail(LNW_EINVAL, "null argument");
-  if (!h->terrain) return fail(LNW_ESTATE, "lnw_load_terrain must be called first");
-  if (action_dtype != LNW_ACT_F32 && action_dtype != LNW_ACT_F64 && action_dtype != LNW_ACT_I32)
-    return fail(LNW_EINVAL, "bad action dtype");
-  if (action_dtype == LNW_ACT_I32 && !h->params.discrete)
-    return fail(LNW_EINVAL, "integer actions go with DISCRETE mode only");
-  if (action_dtype == LNW_ACT_F32 && h->params.discrete)
-    return fail(LNW_EINVAL, "DISCRETE mode takes int32 (ndarray) or float64 (list rows) actions");
-  if ((obs_blue_dev == nullptr) != (obs_red_dev == nullptr))
-    return fail(LNW_EINVAL, "observation outputs: both or neither");
-  KParams k = h->kp;
-  k.act_dtype = action_dtype;
-  k.no_obs = obs_blue_dev == nullptr ? 1 : 0;
-  k.dbg_skip = h->dbg_skip;
-  k.store_wt = h->store_wt;
-  KState s;
-  if (int rc = launch_state(h, s)) return rc;
-  k.qdirect = step_qdirect(h, k.epw) ? 1 : 0;
-  size_t lds = step_launch_lds_bytes(h, k.epw);
-  dim3 grid((h->E + k.epw - 1) / k.epw), block(WAVE);
-  hipStream_t st = (hipStream_t)stream;
-  // (medium ships: 5x5 windows and shorter rows, the runtime-size kernels only)
-  bool generic = h->force_generic;
-  const bool templated = k.los_mode != 2 && !generic && !h->has_medium && h->nb == h->nr && h->nb >= 2 && h->nb <= 4 &&
-                         !(h->force_group && h->group_fits);
-  const bool use_group = k.los_mode != 2 && !templated && !generic && !h->no_group && h->group_fits;
-  // 4v4 at 64 envs per workgroup in LOS-table mode, whole units (the headline):
-  // the units kernel (LNW_NO_UNITS keeps one unit per workgroup)
-  const bool units = templated && h->nb == 4 && !h->contact && !h->no_units && h->units_fit && k.epw == EPW &&
-                     k.los_mode == 0 && h->E % (EPW * UNITS) == 0 && !(h->dbg_skip & (1 | 2 | 512));
-  // per-unit records (LNW_PROF) of the kernel launched below (the group kernel has its own grid)
-  const unsigned nwg = use_group ? (unsigned)((h->E + GEPW - 1) / GEPW) : grid.x;
-  if (h->prof) {
-    const size_t slots = (size_t)nwg * PROF_SLOTS;
-    if (slots > h->prof_cap) {
-      HIPCHK(hipStreamSynchronize(st));
-      if (h->d_prof) { (void)hipFree(h->d_prof); h->d_prof = nullptr; h->prof_cap = 0; }
-      HIPCHK(hipMalloc(&h->d_prof, slots * sizeof(unsigned long long)));
-      h->prof_cap = slots;
-    }
-    HIPCHK(hipMemsetAsync(h->d_prof, 0, slots * sizeof(unsigned long long), st));
-    s.prof = h->d_prof;
-  }
-#define LNW_STEP(NB_, NR_, CW_, RW_)                                                             \
-  step_kernel<NB_, NR_, CW_, RW_><<<grid, dim3(NB_ > 0 && EPW == WAVE ? 2 * WAVE : WAVE), lds, st>>>(k, s, actions_dev, row_kind_dev, obs_blue_dev, \
-                                                 obs_red_dev, rew_blue_dev, rew_red_dev,        \
-                                                 done_dev, cog_dev)
-  const bool cw = h->contact;
-  h->last_kernel = units ? LNW_KERNEL_UNITS
-                   : k.los_mode == 2 ? LNW_KERNEL_REFLOS
-                   : templated ? (cw ? LNW_KERNEL_TEAM_CONTACT : LNW_KERNEL_TEAM)
-                   : use_group ? LNW_KERNEL_GROUP : LNW_KERNEL_GENERIC;
-  if (units) {
-    // 4 units of 64 envs per workgroup, one workgroup per CU (step_kernel UN)
-    step_kernel<4, 4, false, false, UNITS><<<dim3(h->E / (EPW * UNITS)), dim3(2 * WAVE * UNITS),
-                                             (size_t)UNITS * ((lds + 15) & ~(size_t)15), st>>>(
-        k, s, actions_dev, row_kind_dev, obs_blue_dev, obs_red_dev, rew_blue_dev, rew_red_dev, done_dev,
-        cog_dev);
-  }
-  else if (k.los_mode == 2) LNW_STEP(0, 0, false, true);  // diagnostics: the reference's LOS work
-  else if (templated && h->nb == 4) {
-    // the contact variant: phase S split by side (step_kernel PS; LNW_NO_SPLIT_ROWS:
-    // only for steps without rows, A/B)
-    if (cw && k.los_mode == 0 && (k.no_obs || !h->no_split_rows))
-      step_kernel<4, 4, true, false, 1, true><<<grid, dim3(2 * WAVE), lds, st>>>(
-          k, s, actions_dev, row_kind_dev, obs_blue_dev, obs_red_dev, rew_blue_dev, rew_red_dev, done_dev, cog_dev);
-    else if (cw) LNW_STEP(4, 4, true, false);
-    else if (k.qdirect && k.epw * 4 > WAVE)  // two-slab direct rows (step_qdirect)
-      step_kernel<4, 4, false, false, 1, false, true><<<grid, dim3(2 * WAVE), lds, st>>>(
-          k, s, actions_dev, row_kind_dev, obs_blue_dev, obs_red_dev, rew_blue_dev, rew_red_dev, done_dev, cog_dev);
-    else LNW_STEP(4, 4, false, false);
-  }
-  else if (templated && h->nb == 3) { if (cw) LNW_STEP(3, 3, true, false); else LNW_STEP(3, 3, false, false); }
-  else if (templated && h->nb == 2) { if (cw) LNW_STEP(2, 2, true, false); else LNW_STEP(2, 2, false, false); }
-  else if (use_group) {
-    // runtime team sizes: GL lanes per env (lnw_group.inc)
-    const GroupLds gl = group_lds(lds_layout(h->A, h->nb, h->nr, h->nmax, h->G * h->W16, h->G), h->G * h->W16,
-                                  h->A, h->nb * h->nr, k.atan_odd != 0);
-    const size_t glds = (size_t)gl.total;
-    if (s.prof)
-      fprintf(stderr, "[lnw prof] group kernel LDS %zu B (staged: target lists %d, dist_lz %d, bearing half table %d, pooled slopes %d)\n",
-              glds, (int)(gl.tls >= 0), (int)(gl.dlz >= 0), (int)(gl.atab >= 0), (int)(gl.ms >= 0));
-    step_group_kernel<<<dim3((h->E + GEPW - 1) / GEPW), dim3(GEPW * GL), glds, st>>>(
-        k, s, actions_dev, row_kind_dev, obs_blue_dev, obs_red_dev, rew_blue_dev, rew_red_dev,
-        done_dev, cog_dev);
-  }
-  else LNW_STEP(0, 0, false, false);
-#undef LNW_STEP
-  HIPCHK(hipGetLastError());
-  if (s.prof) prof_report(h, st, (int)nwg);
-  return 0;
-}
-}  // namespace
-
-int lnw_step(lnw_handle *h, void *actions_dev, int32_t action_dtype, const uint8_t *row_kind_dev,
-             float *obs_blue_dev, float *obs_red_dev, float *rew_blue_dev, float *rew_red_dev,
-             int32_t *done_dev, float *cog_dev, void *stream) {
-  return step_launch(h, actions_dev, action_dtype, row_kind_dev, obs_blue_dev, obs_red_dev, rew_blue_dev,
-                     rew_red_dev, done_dev, cog_dev, stream);
-}
-
-int lnw_step_seq(lnw_handle *h, const lnw_seq *seq, void *actions_dev, int32_t action_dtype,
-                 const uint8_t *row_kind_dev, float *obs_blue_dev, float *obs_red_dev, float *rew_blue_dev,
-                 float *rew_red_dev, int32_t *done_dev, float *cog_dev, void *stream) {
-  if (!h || !seq) return fail(LNW_EINVAL, "null argument");
-  if (seq->steps < 1) return fail(LNW_EINVAL, "seq->steps must be >= 1");
-  if (seq->act_step < 0 || seq->kind_step < 0 || seq->obs_blue_step < 0 || seq->obs_red_step < 0 ||
-      seq->rew_blue_step < 0 || seq->rew_red_step < 0 || seq->done_step < 0 || seq->cog_step < 0)
-    return fail(LNW_EINVAL, "negative step stride");
-  // K launches back to back on the caller's stream. (Round 5 measured one launch
-  // in which each workgroup ran its envs through the K steps: parity with K
-  // launches at best, DESIGN.md "Action sequences in one call"; removed.)
-  const long long asz = action_dtype == LNW_ACT_F64 ? 8 : 4, rsz = h->kp.rew_f64 ? 8 : 4;
-  for (int k = 0; k < seq->steps; k++) {
-    auto adv = [&](const void *p, long long stride, long long sz) {
-      return p ? (void *)((char *)p + (long long)k * stride * sz) : nullptr;
-    };
-    if (int e = step_launch(h, adv(actions_dev, seq->act_step, asz), action_dtype,
-                            (const uint8_t *)adv(row_kind_dev, seq->kind_step, 1),
-                            (float *)adv(obs_blue_dev, seq->obs_blue_step, 4),
-                            (float *)adv(obs_red_dev, seq->obs_red_step, 4),
-                            (float *)adv(rew_blue_dev, seq->rew_blue_step, rsz),
-                            (float *)adv(rew_red_dev, seq->rew_red_step, rsz),
-                            (int32_t *)adv(done_dev, seq->done_step, 4), (float *)adv(cog_dev, seq->cog_step, rsz),
-                            stream))
-      return e;
-  }
-  return 0;
-}
-
-int lnw_observe(lnw_handle *h, int32_t agent, float *obs_blue_dev, float *obs_red_dev, void *stream) {
-  return lnw_observe_ex(h, agent, obs_blue_dev, 0, obs_red_dev, 0, stream);
-}
-
-int lnw_observe_ex(lnw_handle *h, int32_t agent, float *obs_blue_dev, int64_t blue_env_stride,
-                   float *obs_red_dev, int64_t red_env_stride, void *stream) {
-  if (!h) return fail(LNW_EINVAL, "null handle");
-  if (!h->terrain) return fail(LNW_ESTATE, "lnw_load_terrain must be called first");
-  if (agent >= h->A || agent < LNW_OBS_RED) return fail(LNW_EINVAL, "bad agent selector");
-  const int64_t row_b = (int64_t)h->nb * side_D(h->kp, 0), row_r = (int64_t)h->nr * side_D(h->kp, 1);
-  if (blue_env_stride < 0 || red_env_stride < 0 || (blue_env_stride && (blue_env_stride < row_b || blue_env_stride % 4)) ||
-      (red_env_stride && (red_env_stride < row_r || red_env_stride % 4)))
-    return fail(LNW_EINVAL, "env stride: 0, or a multiple of 4 floats of at least the side's n * D");
-  if (((uintptr_t)obs_blue_dev | (uintptr_t)obs_red_dev) & 15) return fail(LNW_EINVAL, "rows must be 16-B aligned");
-  KState s;
-  if (int rc = launch_state(h, s)) return rc;
-  size_t lds = step_lds_bytes(h);
-  dim3 grid((h->E + h->kp.epw - 1) / h->kp.epw), block(WAVE);
-  hipStream_t st = (hipStream_t)stream;
-  const bool tmpl = !h->force_generic && !h->has_medium && h->params.los_mode != 2 && h->nb == h->nr;
-  const bool cw = h->contact;
-  KParams k = h->kp;
-  k.obs_stride[0] = blue_env_stride;
-  k.obs_stride[1] = red_env_stride;
-#define LNW_OBS(NB_, CW_)                                                                          \
-  observe_kernel<NB_, NB_, CW_><<<grid, dim3(NB_ > 0 && CW_ ? 2 * WAVE : WAVE), lds, st>>>(k, s, agent, \
-                                                                                    obs_blue_dev, obs_red_dev)
-  if (tmpl && h->nb == 4) { if (cw) LNW_OBS(4, true); else LNW_OBS(4, false); }
-  else if (tmpl && h->nb == 3) { if (cw) LNW_OBS(3, true); else LNW_OBS(3, false); }
-  else if (tmpl && h->nb == 2) { if (cw) LNW_OBS(2, true); else LNW_OBS(2, false); }
-  else LNW_OBS(0, false);
-#undef LNW_OBS
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-int lnw_state_field(lnw_handle *h, int32_t field, void **dev_ptr, int64_t *nbytes) {
-  if (!h || !dev_ptr || !nbytes) return fail(LNW_EINVAL, "null argument");
-  const int64_t E = h->E, A = h->A;
-  switch (field) {
-    case LNW_F_POS: *dev_ptr = h->pos; *nbytes = 4 * A * E; break;
-    case LNW_F_RADAR: *dev_ptr = h->radar; *nbytes = 4 * A * E; break;
-    case LNW_F_MISSILES: *dev_ptr = h->miss; *nbytes = A * E; break;
-    case LNW_F_MKIND: *dev_ptr = h->mkind; *nbytes = A * E; break;
-    case LNW_F_ALIVE: *dev_ptr = h->alive; *nbytes = A * E; break;
-    case LNW_F_TYPE: *dev_ptr = h->type; *nbytes = A * E; break;
-    case LNW_F_STEPS: *dev_ptr = h->steps; *nbytes = 4 * A * E; break;
-    case LNW_F_DIST_LZ: *dev_ptr = h->dist_lz; *nbytes = 8 * A * E; break;
-    case LNW_F_TL_CNT: *dev_ptr = h->tl_cnt; *nbytes = 2 * A * E; break;
-    case LNW_F_TL: *dev_ptr = h->tl; *nbytes = 2 * A * h->T * E; break;
-    case LNW_F_DUCT: *dev_ptr = h->duct; *nbytes = 8 * E; break;
-    case LNW_F_ENV: *dev_ptr = h->envi; *nbytes = 4 * 8 * E; break;
-    case LNW_F_RNG: *dev_ptr = h->rng; *nbytes = 8 * E; break;
-    case LNW_F_ERR: *dev_ptr = h->err; *nbytes = 4 * E; break;
-    default: return fail(LNW_EINVAL, "unknown state field");
-  }
-  return 0;
-}
-
-int lnw_tlist_cap(lnw_handle *h) { return h ? h->T : LNW_EINVAL; }
-
-int lnw_step_kernel(lnw_handle *h) { return h ? h->last_kernel : LNW_EINVAL; }
-
-// ---- whole-state snapshots (lnw_state_bytes / lnw_get_state / lnw_set_state)
-// Snapshot layout: a 128-byte header (below), then the LNW_NFIELDS state
-// fields in field order, then the spawn spec the in-kernel auto-reset reads
-// (types, cells, randint flags: 64 x i32, 64 x 2 x i32, 64 x i32) and the
-// per-env spawn cells ([E][A][2] i32, zeros when the last reset had none);
-// every section starts on a 256-byte boundary.
-namespace {
-struct StateHeader {
-  char magic[8];            // "LNWSTATE"
-  uint32_t version;         // 1
-  int32_t E, nb, nr, T, G;
-  int32_t rng_mode;         // LNW_RNG_*
-  int32_t pos_env_on;       // the auto-reset respawns on per-env cells
-  uint64_t seed;
-  uint64_t terrain_hash;    // FNV-1a of the grid loaded when the snapshot was taken
-  int64_t total;            // snapshot bytes
-  int32_t box_lo[2], box_hi[2];
-  int32_t abi;              // LNW_ABI_VERSION
-  uint8_t pad[128 - 8 - 4 - 7 * 4 - 3 * 8 - 4 * 4 - 4];
-};
-static_assert(sizeof(StateHeader) == 128, "state header is 128 bytes");
-
-struct Section { void *dev; int64_t bytes; };
-
-int state_sections(lnw_handle *h, std::vector<Section> &out) {
-  out.clear();
-  for (int f = 0; f < LNW_NFIELDS; f++) {
-    void *p = nullptr;
-    int64_t n = 0;
-    if (int rc = lnw_state_field(h, f, &p, &n)) return rc;
-    out.push_back({p, n});
-  }
-  out.push_back({h->sp_types, 64 * 4});
-  out.push_back({h->sp_pos, 128 * 4});
-  out.push_back({h->sp_randls, 64 * 4});
-  out.push_back({h->sp_pos_env, (int64_t)h->E * h->A * 2 * 4});  // (may not be allocated yet)
-  return 0;
-}
-
-inline int64_t sec_align(int64_t v) { return (v + 255) & ~(int64_t)255; }
-}  // namespace
-
-int64_t lnw_state_bytes(lnw_handle *h) {
-  if (!h) return fail(LNW_EINVAL, "null handle");
-  std::vector<Section> s;
-  if (int rc = state_sections(h, s)) return rc;
-  int64_t o = 256;
-  for (const Section &x : s) o += sec_align(x.bytes);
-  return o;
-}
-
-int lnw_get_state(lnw_handle *h, void *dst, int64_t nbytes, void *stream) {
-  if (!h || !dst) return fail(LNW_EINVAL, "null argument");
-  if (!h->terrain) return fail(LNW_ESTATE, "lnw_load_terrain must be called first");
-  const int64_t total = lnw_state_bytes(h);
-  if (nbytes < total) return fail(LNW_EINVAL, "snapshot buffer smaller than lnw_state_bytes()");
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-  StateHeader hd;
-  memset(&hd, 0, sizeof hd);
-  memcpy(hd.magic, "LNWSTATE", 8);
-  hd.version = 1;
-  hd.E = h->E; hd.nb = h->nb; hd.nr = h->nr; hd.T = h->T; hd.G = h->G;
-  hd.rng_mode = h->kp.rng_mode;
-  hd.pos_env_on = h->sp_pos_env_on ? 1 : 0;
-  hd.seed = h->kp.seed;
-  hd.terrain_hash = h->terrain_hash;
-  hd.total = total;
-  for (int i = 0; i < 2; i++) { hd.box_lo[i] = h->kp.box_lo[i]; hd.box_hi[i] = h->kp.box_hi[i]; }
-  hd.abi = LNW_ABI_VERSION;
-  std::vector<Section> s;
-  if (int rc = state_sections(h, s)) return rc;
-  char *d = (char *)dst;
-  char hbuf[256] = {0};
-  memcpy(hbuf, &hd, sizeof hd);
-  HIPCHK(hipMemcpy(d, hbuf, sizeof hbuf, hipMemcpyDefault));
-  int64_t o = 256;
-  for (const Section &x : s) {
-    if (x.dev) {
-      HIPCHK(hipMemcpy(d + o, x.dev, (size_t)x.bytes, hipMemcpyDefault));
-    } else {  // per-env spawn cells never given: zeros (host or device destination)
-      const std::vector<char> z((size_t)x.bytes, 0);
-      HIPCHK(hipMemcpy(d + o, z.data(), (size_t)x.bytes, hipMemcpyDefault));
-    }
-    o += sec_align(x.bytes);
-  }
-  return 0;
-}
-
-int lnw_set_state(lnw_handle *h, const void *src, int64_t nbytes, void *stream) {
-  if (!h || !src) return fail(LNW_EINVAL, "null argument");
-  if (!h->terrain) return fail(LNW_ESTATE, "lnw_load_terrain must be called first");
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-  if (nbytes < (int64_t)sizeof(StateHeader)) return fail(LNW_EINVAL, "snapshot too short");
-  StateHeader hd;
-  HIPCHK(hipMemcpy(&hd, src, sizeof hd, hipMemcpyDefault));
-  if (memcmp(hd.magic, "LNWSTATE", 8) != 0 || hd.version != 1)
-    return fail(LNW_EINVAL, "not an lnw state snapshot (bad magic or version)");
-  if (hd.abi != LNW_ABI_VERSION)
-    return fail(LNW_EINVAL, "snapshot was taken by a library of another ABI version");
-  const int64_t total = lnw_state_bytes(h);
-  if (hd.E != h->E || hd.nb != h->nb || hd.nr != h->nr || hd.T != h->T || hd.G != h->G || hd.total != total)
-    return fail(LNW_EINVAL, "snapshot shape (envs, team sizes, grid) differs from this handle");
-  if (hd.terrain_hash != h->terrain_hash) return fail(LNW_EINVAL, "snapshot was taken on another terrain");
-  if (nbytes < total) return fail(LNW_EINVAL, "snapshot shorter than its header says");
-  if (hd.rng_mode == LNW_RNG_TAPE && (!h->tape || !h->tape_off))
-    return fail(LNW_ESTATE, "snapshot is in tape mode: bind the tape (lnw_set_rng) before restoring");
-  if (hd.pos_env_on && !h->sp_pos_env && dalloc(h, &h->sp_pos_env, (size_t)h->E * h->A * 2)) return LNW_ENOMEM;
-  std::vector<Section> s;
-  if (int rc = state_sections(h, s)) return rc;
-  const char *p = (const char *)src;
-  // the spawn types decide the kernels and the row lengths (wc, has_medium):
-  // validate them before anything is overwritten, apply them after
-  int32_t types[64];
-  {
-    int64_t ot = 256;
-    for (int i = 0; i < LNW_NFIELDS; i++) ot += sec_align(s[i].bytes);
-    HIPCHK(hipMemcpy(types, p + ot, sizeof types, hipMemcpyDefault));
-    if (int rc = apply_side_types(h, types, false)) return rc;
-  }
-  int64_t o = 256;
-  for (const Section &x : s) {
-    if (x.dev) HIPCHK(hipMemcpy(x.dev, p + o, (size_t)x.bytes, hipMemcpyDefault));
-    o += sec_align(x.bytes);
-  }
-  apply_side_types(h, types, true);
-  h->kp.rng_mode = hd.rng_mode;
-  if (hd.rng_mode == LNW_RNG_PHILOX) h->kp.seed = hd.seed;
-  for (int i = 0; i < 2; i++) { h->kp.box_lo[i] = hd.box_lo[i]; h->kp.box_hi[i] = hd.box_hi[i]; }
-  h->sp_pos_env_on = hd.pos_env_on != 0;
-  return cold_commit(h, nullptr);
-}
-
-int lnw_set_counters(lnw_handle *h, uint64_t *counters_dev) {
-  if (!h) return fail(LNW_EINVAL, "null handle");
-  h->ctr = (unsigned long long *)counters_dev;
-  return cold_commit(h, nullptr);
-}
-
-int lnw_set_reward_dtype(lnw_handle *h, int32_t f64) {
-  if (!h) return fail(LNW_EINVAL, "null handle");
-  h->kp.rew_f64 = f64 != 0;
-  return 0;
-}
-
-int lnw_set_variant(lnw_handle *h, int32_t contact) {
-  if (!h) return fail(LNW_EINVAL, "null handle");
-  h->contact = contact != 0;
-  return 0;
-}
-
-int lnw_set_epw(lnw_handle *h, int32_t epw) {
-  if (!h) return fail(LNW_EINVAL, "null handle");
-  if (epw < 0 || epw > EPW) return fail(LNW_EINVAL, "epw must be 0 (automatic) or 1..64");
-  if (!h->terrain) return fail(LNW_ESTATE, "lnw_load_terrain must be called first");
-  h->kp.epw = epw ? epw : choose_epw(h);
-  return h->kp.epw;
-}
-
-int lnw_los_batch(const uint8_t *grid_dev, int32_t G, const int16_t *pairs_dev, int64_t n,
-                  int32_t move_thr, int32_t ew_thr, uint8_t *out_dev, void *stream) {
-  if (!grid_dev || !pairs_dev || !out_dev) return fail(LNW_EINVAL, "null argument");
-  if (n <= 0) return 0;
-  const size_t lds = (size_t)G * ((G + 15) / 16) * 4;
-  if (lds <= 64 * 1024 && ((uintptr_t)pairs_dev & 7) == 0) {  // (the LDS kernel reads a pair as 8 bytes)
-    const long long per_block = (long long)(LB_THREADS / WAVE) * LB_RAYS_PER_WAVE;
-    los_batch_kernel<<<(unsigned)((n + per_block - 1) / per_block), LB_THREADS, lds, (hipStream_t)stream>>>(
-        grid_dev, G, pairs_dev, n, move_thr, ew_thr, out_dev);
-  } else {
-    los_batch_global_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(
-        grid_dev, G, pairs_dev, n, move_thr, ew_thr, out_dev);
-  }
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-int lnw_astar_batch(const uint8_t *grid_dev, int32_t G, int32_t move_thr, const int8_t *types_dev,
-                    const int16_t *start_dev, const int16_t *target_dev, int64_t n,
-                    int16_t *plen_dev, int8_t *kind_dev, uint8_t *feasible_dev, void *stream) {
-  if (!grid_dev || !types_dev || !start_dev || !target_dev || !plen_dev || !kind_dev || !feasible_dev)
-    return fail(LNW_EINVAL, "null argument");
-  if (n <= 0) return 0;
-  astar_batch_kernel<<<(unsigned)((n + WAVE - 1) / WAVE), WAVE, 0, (hipStream_t)stream>>>(
-      grid_dev, G, move_thr, types_dev, start_dev, target_dev, n, plen_dev, kind_dev, feasible_dev);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-int lnw_move_batch(lnw_handle *h, const int8_t *types_dev, const int16_t *pos_dev,
-                   const double *act_dev, const uint8_t *is_f32_dev, int64_t n, int32_t *rounded_dev,
-                   uint8_t *ok_dev, void *stream) {
-  if (!h || !types_dev || !pos_dev || !act_dev || !is_f32_dev || !rounded_dev || !ok_dev)
-    return fail(LNW_EINVAL, "null argument");
-  if (!h->terrain) return fail(LNW_ESTATE, "lnw_load_terrain must be called first");
-  if (n <= 0) return 0;
-  KState s;
-  if (int rc = launch_state(h, s)) return rc;
-  move_batch_kernel<<<(unsigned)((n + WAVE - 1) / WAVE), WAVE, 0, (hipStream_t)stream>>>(
-      h->kp, s, types_dev, pos_dev, act_dev, is_f32_dev, n, rounded_dev, ok_dev);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-int lnw_path_query(lnw_handle *h, const int8_t *types_dev, const int16_t *start_dev,
-                   const int16_t *target_dev, int64_t n, uint8_t *out_dev, void *stream) {
-  if (!h || !types_dev || !start_dev || !target_dev || !out_dev) return fail(LNW_EINVAL, "null argument");
-  if (!h->terrain) return fail(LNW_ESTATE, "lnw_load_terrain must be called first");
-  if (n <= 0) return 0;
-  KState s;
-  if (int rc = launch_state(h, s)) return rc;
-  path_query_kernel<<<(unsigned)((n + WAVE - 1) / WAVE), WAVE, 0, (hipStream_t)stream>>>(
-      h->kp, s, types_dev, start_dev, target_dev, n, out_dev);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-int lnw_los_query(lnw_handle *h, const int16_t *pairs_dev, int64_t n, uint8_t *out_dev, void *stream) {
-  if (!h || !pairs_dev || !out_dev) return fail(LNW_EINVAL, "null argument");
-  if (!h->terrain) return fail(LNW_ESTATE, "lnw_load_terrain must be called first");
-  if (n <= 0) return 0;
-  KState s;
-  if (int rc = launch_state(h, s)) return rc;
-  los_query_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(h->kp, s, pairs_dev, n, out_dev);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-int lnw_copy(void *dst, const void *src, int64_t nbytes, void *stream) {
-  if (nbytes <= 0) return 0;
-  if (!dst || !src) return fail(LNW_EINVAL, "null argument");
-  HIPCHK(hipMemcpyAsync(dst, src, (size_t)nbytes, hipMemcpyDefault, (hipStream_t)stream));
-  return 0;
-}
-
-int lnw_fill_uniform_f32(float *out_dev, int64_t n, uint64_t seed, uint64_t offset, void *stream) {
-  if (!out_dev) return fail(LNW_EINVAL, "null argument");
-  if (n <= 0) return 0;
-  if (offset & 3) return fail(LNW_EINVAL, "offset must be a multiple of 4");
-  long long nt = (n + 3) / 4;
-  fill_uniform_kernel<<<(unsigned)((nt + 255) / 256), 256, 0, (hipStream_t)stream>>>(out_dev, n, seed, offset);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-}  // extern "C"
+#include "lnw_host.inc"

@@ -293,8 +293,7 @@ __device__ __forceinline__ void quiet_moves_t(Cols &c, int lane) {
   for (int k = 0; k < N; k++) {
     const int a = W + 2 * k;
     if (!al[k]) continue;
-    const double rr = rint(a0[k]);
-    COLW(c.radar_cur, a) = (int)fmin(fmax(rr, -2147483648.0), 2147483647.0);
+    COLW(c.radar_cur, a) = radar_setting(a0[k]);
     if (pn[k] & 0x80000000u) COLW(c.pos_cur, a) = pn[k] & 0x7fffffffu;
   }
 }

@@ -20,9 +20,10 @@ DIAG_OUT = os.path.join(HERE, "liblnw_diag.so")
 DIAG_DEFINES = ("LNW_DIAG", "LNW_GROUP_PROF")
 SOURCES = [os.path.join(CSRC, "lnw_kernels.hip"), os.path.join(CSRC, "lnw_actor.hip"),
            os.path.join(CSRC, "lnw_qnet.hip"), os.path.join(CSRC, "lnw_qlearn.hip")]
-DEPS = SOURCES + [os.path.join(CSRC, "lnw_device.h"), os.path.join(CSRC, "lnw_quiet.inc"),
-                  os.path.join(CSRC, "lnw_group.inc"), os.path.join(CSRC, "lnw_convhead.inc"),
-                  os.path.join(CSRC, "lnw_qhead.inc"), os.path.join(INCLUDE, "lnw.h")]
+# everything a source can include: csrc's own files and the C-ABI header
+# (csrc/ holds library sources only: a stray file there changes source_digest())
+DEPS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC)
+              if f.endswith((".hip", ".h", ".inc"))) + [os.path.join(INCLUDE, "lnw.h")]
 
 
 def hipcc():
