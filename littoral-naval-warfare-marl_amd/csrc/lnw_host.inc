@@ -1,8 +1,9 @@
-// lnw_host.inc — the host side of liblnw: error handling, lnw_handle, LDS
-// sizing, the kernel launches and the C-ABI of include/lnw.h (lnw_create ..
-// lnw_copy, state snapshots). Included last by lnw_kernels.hip, still inside the
-// anonymous namespace the kernels opened: the kernel templates are launched
-// from here, so it is the same translation unit.
+// lnw_host.inc — the host side of liblnw: error handling, lnw_handle, the
+// kernel tables and launch planning (STEP_KERNELS, OBS_KERNELS, plan_step,
+// plan_observe, choose_epw), the kernel launches and the C-ABI of include/lnw.h
+// (lnw_create .. lnw_copy, state snapshots). Included last by lnw_kernels.hip,
+// still inside the anonymous namespace the kernels opened: the kernel templates
+// are launched from here, so it is the same translation unit.
 
 // ===========================================================================
 // host side
@@ -44,8 +45,28 @@ void host_constants(KParams &k) {
 
 }  // namespace
 
+// The environment knobs of a handle. Constructing one reads them: once, as
+// lnw_create makes the handle. (LNW_EPW_RT alone is read where it acts, in choose_epw.)
+struct Knobs {
+  static bool on(const char *name) { return getenv(name) != nullptr; }
+  int dbg_skip = on("LNW_DEBUG_SKIP") ? atoi(getenv("LNW_DEBUG_SKIP")) : 0;  // (checked by lnw_create)
+  bool prof = on("LNW_PROF");                    // per-workgroup phase timestamps and their report
+  bool force_generic = on("LNW_FORCE_GENERIC");  // the runtime-size kernels for every team shape
+  bool no_group = on("LNW_NO_GROUP");            // runtime team sizes on the one-lane-per-env kernel (A/B tests)
+  bool force_group = on("LNW_FORCE_GROUP");      // (A/B) the group kernel for templated team sizes too
+  bool no_split_rows = on("LNW_NO_SPLIT_ROWS");  // (A/B) row-writing contact steps keep phase S on one wave
+  bool no_units = on("LNW_NO_UNITS");            // one 64-env unit per workgroup for the headline shape (A/B tests)
+  bool no_slab = on("LNW_NO_SLAB");              // no two-slab direct rows (A/B)
+  bool no_xcd_remap = on("LNW_NO_XCD_REMAP");    // KParams.xcd_remap off (A/B)
+  // LNW_GROUP_MARCH=1: the group kernel marches its pair LOS over the LDS
+  // terrain mask instead of loading LOS-table words (A/B)
+  bool group_march = on("LNW_GROUP_MARCH");
+  bool no_store_wt = on("LNW_NO_STORE_WT");      // non-temporal observation stores kept (A/B)
+};
+
 struct lnw_handle {
   int device = 0;
+  Knobs knobs;
   lnw_params params{};
   KParams kp{};
   // device copies of every distinct cold block this handle has launched with,
@@ -63,14 +84,11 @@ struct lnw_handle {
   size_t prof_cap = 0;                   // d_prof capacity in slots (grown to the launch grid)
   lnw_analytics ana{};                   // bound analytics buffers (lnw_set_analytics)
   unsigned long long *ctr = nullptr;     // bound work counters (lnw_set_counters)
-  // diagnostics knobs, read once at lnw_create (LNW_DEBUG_SKIP / LNW_PROF / LNW_FORCE_GENERIC)
-  int dbg_skip = 0;
-  bool prof = false, force_generic = false, no_group = false, group_fits = false, no_units = false;
-  bool no_slab = false;  // LNW_NO_SLAB: no two-slab direct rows (A/B)
-  bool force_group = false;  // LNW_FORCE_GROUP (A/B): the group kernel for templated team sizes too
-  bool no_split_rows = false;  // LNW_NO_SPLIT_ROWS (A/B): row-writing contact steps keep phase S on one wave
   bool store_wt = false;
-  bool units_fit = false;  // UNITS blocks of the step layout fit one workgroup (lnw_load_terrain)
+  // fixed by lnw_load_terrain (the LDS sizes depend on the grid):
+  bool group_fits = false;  // the group kernel's required LDS parts fit (else runtime sizes stay on step_kernel<0, 0>)
+  GroupLds group_lds{};     // the group kernel's dynamic LDS (total bytes, which optional parts are staged)
+  bool units_fit = false;   // UNITS blocks of the step layout fit one workgroup
   bool contact = false;  // lnw_set_variant: contact-heavy phase-S code in the templated kernels
   int last_kernel = LNW_KERNEL_NONE;     // lnw_step_kernel: what the last lnw_step launched
   bool has_medium = false;               // the spawn spec has medium ships (runtime-size kernels only)
@@ -157,14 +175,7 @@ int launch_state(lnw_handle *h, KState &s) {
   return cold_commit(h, &s.cold);
 }
 
-size_t step_lds_bytes(const lnw_handle *h) {
-  LdsLayout L = lds_layout(h->A, h->nb, h->nr, h->nmax, h->G * h->W16, h->G);
-  return (size_t)L.total;
-}
-
-// the step launch's LDS: step_lds_bytes plus the whole-side row stages of
-// small quiet workgroups (the same condition step_kernel evaluates)
-// compute units of the handle's device (cached per device)
+// compute units of a device (cached per device; the one place that asks the runtime)
 int device_ncu(int dev) {
   static int cache[64] = {0};
   int &c = cache[dev & 63];
@@ -175,6 +186,72 @@ int device_ncu(int dev) {
   return c;
 }
 
+// ===========================================================================
+// launch planning: which kernel, grid, block and LDS a step or observe launch
+// takes (plan_step, plan_observe), and the envs per workgroup (choose_epw).
+// The plans read the handle only; nothing here makes a HIP call but device_ncu.
+// ===========================================================================
+using StepFn = void (*)(KParams, KState, void *, const uint8_t *, float *, float *, float *, float *, int32_t *,
+                        float *);
+using ObsFn = void (*)(KParams, KState, int, float *, float *);
+
+// One kernel the host can launch: its public code (LNW_KERNEL_*; for an observe
+// kernel, that of the step kernel it pairs with), its threads per workgroup
+// (the kernel's __launch_bounds__) and the dynamic LDS lnw_load_terrain opts it
+// in for. A kernel is launched only through its row, so it cannot miss the opt-in.
+template <class Fn>
+struct KernelRow { Fn fn; int code, threads, lds_cap; };
+
+constexpr int TEAM_THREADS = EPW == WAVE ? 2 * WAVE : WAVE;  // step_kernel<N, N> with N > 0
+
+// rows of STEP_KERNELS; the plain n-v-n kernels sit at SK_2V2 + 2 * (n - 2) + contact
+enum StepK {
+  SK_GENERIC, SK_REFLOS, SK_GROUP, SK_2V2, SK_2V2_CONTACT, SK_3V3, SK_3V3_CONTACT, SK_4V4, SK_4V4_CONTACT,
+  SK_4V4_SPLIT, SK_4V4_SLAB, SK_UNITS, SK_COUNT
+};
+const KernelRow<StepFn> STEP_KERNELS[] = {
+    {step_kernel<0, 0>, LNW_KERNEL_GENERIC, WAVE, GROUP_LDS_MAX},
+    {step_kernel<0, 0, false, true>, LNW_KERNEL_REFLOS, WAVE, GROUP_LDS_MAX},  // diagnostics: the reference's LOS work
+    {step_group_kernel, LNW_KERNEL_GROUP, GEPW * GL, GROUP_LDS_MAX},  // runtime team sizes: GL lanes per env (lnw_group.inc)
+    {step_kernel<2, 2>, LNW_KERNEL_TEAM, TEAM_THREADS, GROUP_LDS_MAX},
+    {step_kernel<2, 2, true>, LNW_KERNEL_TEAM_CONTACT, TEAM_THREADS, GROUP_LDS_MAX},
+    {step_kernel<3, 3>, LNW_KERNEL_TEAM, TEAM_THREADS, GROUP_LDS_MAX},
+    {step_kernel<3, 3, true>, LNW_KERNEL_TEAM_CONTACT, TEAM_THREADS, GROUP_LDS_MAX},
+    {step_kernel<4, 4>, LNW_KERNEL_TEAM, TEAM_THREADS, GROUP_LDS_MAX},
+    {step_kernel<4, 4, true>, LNW_KERNEL_TEAM_CONTACT, TEAM_THREADS, GROUP_LDS_MAX},
+    // the contact variant with phase S split by side (step_kernel PS)
+    {step_kernel<4, 4, true, false, 1, true>, LNW_KERNEL_TEAM_CONTACT, TEAM_THREADS, GROUP_LDS_MAX},
+    // two-slab direct rows (step_kernel SL, step_qdirect)
+    {step_kernel<4, 4, false, false, 1, false, true>, LNW_KERNEL_TEAM, TEAM_THREADS, GROUP_LDS_MAX},
+    // 4 units of 64 envs per workgroup, one workgroup per CU (step_kernel UN)
+    {step_kernel<4, 4, false, false, UNITS>, LNW_KERNEL_UNITS, TEAM_THREADS * UNITS, UNITS_LDS_MAX},
+};
+static_assert(sizeof STEP_KERNELS / sizeof STEP_KERNELS[0] == SK_COUNT, "one row per StepK");
+
+// the runtime-size kernel, then the n-v-n kernels at 1 + 2 * (n - 2) + contact
+// (two waves for the contact shapes only: blue's calls on wave 0, red's on wave 1)
+const KernelRow<ObsFn> OBS_KERNELS[] = {
+    {observe_kernel<0, 0, false>, LNW_KERNEL_GENERIC, WAVE, GROUP_LDS_MAX},
+    {observe_kernel<2, 2, false>, LNW_KERNEL_TEAM, WAVE, GROUP_LDS_MAX},
+    {observe_kernel<2, 2, true>, LNW_KERNEL_TEAM_CONTACT, 2 * WAVE, GROUP_LDS_MAX},
+    {observe_kernel<3, 3, false>, LNW_KERNEL_TEAM, WAVE, GROUP_LDS_MAX},
+    {observe_kernel<3, 3, true>, LNW_KERNEL_TEAM_CONTACT, 2 * WAVE, GROUP_LDS_MAX},
+    {observe_kernel<4, 4, false>, LNW_KERNEL_TEAM, WAVE, GROUP_LDS_MAX},
+    {observe_kernel<4, 4, true>, LNW_KERNEL_TEAM_CONTACT, 2 * WAVE, GROUP_LDS_MAX},
+};
+
+// The team-shape test, written once: equal sides of 2..4 ships have kernels with
+// compile-time sizes and two waves per workgroup. Each user adds its own further
+// conditions where it applies this; they differ (DESIGN.md, "Kernel variants").
+bool team_shape(const lnw_handle *h) {
+  return !h->knobs.force_generic && h->nb == h->nr && h->nb >= 2 && h->nb <= 4 && EPW == WAVE;
+}
+
+// LDS of the step layout, with row stages for `rows` rows per side (lds_layout's qbig)
+size_t step_lds_bytes(const lnw_handle *h, int rows = 0) {
+  return (size_t)lds_layout(h->A, h->nb, h->nr, h->nmax, h->G * h->W16, h->G, rows).total;
+}
+
 // Quiet workgroups' direct rows (quiet_step_t): a workgroup of up to 64 / nb envs
 // stages both sides' rows whole (qbig) and wave 1 builds and stores every row
 // from registers; up to 128 / nb envs it does so in two slabs of 64 / nb envs,
@@ -182,22 +259,82 @@ int device_ncu(int dev) {
 // grid at once (config 3 at N = 4: 16 384 envs, 32 per workgroup). Larger
 // workgroups stream their rows in staged passes (quiet_emit_t).
 bool step_qdirect(const lnw_handle *h, int epw) {
-  const bool tmpl = !h->force_generic && !h->has_medium && h->params.los_mode == 0 && h->nb == h->nr &&
-                    h->nb >= 2 && h->nb <= 4 && EPW == WAVE;
-  if (!tmpl) return false;
+  // LOS-table mode and no medium ships only; LNW_FORCE_GROUP is not looked at
+  // (the group kernel is still passed this value in KParams)
+  if (!team_shape(h) || h->has_medium || h->params.los_mode != 0) return false;
   if (epw * h->nb <= WAVE) return true;
   // (4v4 only: step_kernel<4, 4, .., SL> is the one two-slab instantiation)
-  if (h->nb != 4 || h->contact || h->no_slab || epw * h->nb > 2 * WAVE) return false;
-  const LdsLayout L = lds_layout(h->A, h->nb, h->nr, h->nmax, h->G * h->W16, h->G, WAVE);
-  int per_cu = (int)((160 * 1024) / ((size_t)L.total + 1024));
+  if (h->nb != 4 || h->contact || h->knobs.no_slab || epw * h->nb > 2 * WAVE) return false;
+  int per_cu = (int)((160 * 1024) / (step_lds_bytes(h, WAVE) + 1024));
   if (per_cu > 4) per_cu = 4;  // 256 VGPRs: two waves per SIMD
   return (h->E + epw - 1) / epw <= (long long)device_ncu(h->device) * per_cu;
 }
 
+// the step launch's LDS: step_lds_bytes plus the whole-side row stages of
+// small quiet workgroups (the same condition step_kernel evaluates)
 size_t step_launch_lds_bytes(const lnw_handle *h, int epw) {
-  const int rows = step_qdirect(h, epw) ? (epw * h->nb < WAVE ? epw * h->nb : WAVE) : 0;
-  LdsLayout L = lds_layout(h->A, h->nb, h->nr, h->nmax, h->G * h->W16, h->G, rows);
-  return (size_t)L.total;
+  return step_lds_bytes(h, step_qdirect(h, epw) ? (epw * h->nb < WAVE ? epw * h->nb : WAVE) : 0);
+}
+
+// One step launch, decided: the kernel's table row, its launch shape, KParams'
+// qdirect and the number of LNW_PROF records the launch writes (nwg).
+struct StepPlan {
+  const KernelRow<StepFn> *row;
+  unsigned grid, block, nwg;
+  size_t lds;
+  bool qdirect;
+};
+
+StepPlan plan_step(const lnw_handle *h, int epw, bool no_obs) {
+  const Knobs &kn = h->knobs;
+  const int los = h->params.los_mode;
+  const bool cw = h->contact;
+  // compile-time sizes: not the reference's LOS work, not medium ships (5x5
+  // windows and shorter rows, the runtime-size kernels only), and not under
+  // LNW_FORCE_GROUP where the group kernel can run
+  const bool templated = team_shape(h) && los != 2 && !h->has_medium && !(kn.force_group && h->group_fits);
+  const bool group = los != 2 && !templated && !kn.force_generic && !kn.no_group && h->group_fits;
+  // 4v4 at 64 envs per workgroup in LOS-table mode, whole units (the headline):
+  // the units kernel (LNW_NO_UNITS keeps one unit per workgroup)
+  const bool units = templated && h->nb == 4 && !cw && !kn.no_units && h->units_fit && epw == EPW && los == 0 &&
+                     h->E % (EPW * UNITS) == 0 && !(kn.dbg_skip & (1 | 2 | 512));
+  StepPlan p;
+  p.qdirect = step_qdirect(h, epw);
+  int r = group ? SK_GROUP : SK_GENERIC;
+  if (units) r = SK_UNITS;
+  else if (los == 2) r = SK_REFLOS;
+  // the contact variant with phase S split by side (LNW_NO_SPLIT_ROWS: only for steps without rows, A/B)
+  else if (templated && h->nb == 4 && cw && los == 0 && (no_obs || !kn.no_split_rows)) r = SK_4V4_SPLIT;
+  else if (templated && h->nb == 4 && !cw && p.qdirect && epw * 4 > WAVE) r = SK_4V4_SLAB;
+  else if (templated) r = SK_2V2 + 2 * (h->nb - 2) + (cw ? 1 : 0);
+  p.row = &STEP_KERNELS[r];
+  p.block = (unsigned)p.row->threads;
+  // one LNW_PROF record per unit of epw envs, or per workgroup of the group kernel
+  p.grid = p.nwg = (unsigned)((h->E + epw - 1) / epw);
+  p.lds = step_launch_lds_bytes(h, epw);
+  if (units) {
+    p.grid = (unsigned)(h->E / (EPW * UNITS));
+    p.lds = (size_t)UNITS * ((p.lds + 15) & ~(size_t)15);
+  } else if (group) {
+    p.grid = p.nwg = (unsigned)((h->E + GEPW - 1) / GEPW);
+    p.lds = (size_t)h->group_lds.total;
+  }
+  return p;
+}
+
+// lnw_observe's launch: the step layout without row stages, at the handle's
+// epw. Unlike plan_step it does not look at LNW_FORCE_GROUP (there is no group
+// observe kernel).
+struct ObsPlan {
+  const KernelRow<ObsFn> *row;
+  unsigned grid, block;
+  size_t lds;
+};
+
+ObsPlan plan_observe(const lnw_handle *h) {
+  const bool templated = team_shape(h) && !h->has_medium && h->params.los_mode != 2;
+  const KernelRow<ObsFn> *row = &OBS_KERNELS[templated ? 1 + 2 * (h->nb - 2) + (h->contact ? 1 : 0) : 0];
+  return {row, (unsigned)((h->E + h->kp.epw - 1) / h->kp.epw), (unsigned)row->threads, step_lds_bytes(h)};
 }
 
 // Environments per workgroup: EPW (one env per lane) unless that leaves the GPU
@@ -211,11 +348,11 @@ int choose_epw(const lnw_handle *h) {
     int v = atoi(e);
     if (v >= 1 && v <= EPW) return v;
   }
-  int ncu = 256;
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, h->device) == hipSuccess && prop.multiProcessorCount > 0)
-    ncu = prop.multiProcessorCount;
-  const bool two_wave = !h->force_generic && h->params.los_mode != 2 && h->nb == h->nr && h->nb >= 2 && h->nb <= 4 && EPW == WAVE;
+  const int ncu = device_ncu(h->device);
+  // epw is chosen (lnw_load_terrain) before a reset can set has_medium or
+  // lnw_set_variant the contact flag, and LNW_FORCE_GROUP is not looked at: the
+  // shape counts as two-wave unless the reference's LOS work excludes it
+  const bool two_wave = team_shape(h) && h->params.los_mode != 2;
   const int by_waves = two_wave ? 4 : 8;  // 256 VGPRs: two waves per SIMD
   // resident workgroups at a given epw (the launch's LDS depends on it: small
   // quiet workgroups carry whole-side row stages)
@@ -237,229 +374,6 @@ int choose_epw(const lnw_handle *h) {
 }
 
 }  // namespace
-
-// LNW_PROF diagnostics: mean per-workgroup phase spans and the grid-wide
-// start / end spread of one step launch (synchronises the stream).
-void prof_report(lnw_handle *h, hipStream_t st, int nwg) {
-  std::vector<unsigned long long> t((size_t)nwg * PROF_SLOTS);
-  if (hipMemcpyAsync(t.data(), h->d_prof, t.size() * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess)
-    return;
-  double sL = 0, sM = 0, sS = 0, sW = 0, s1 = 0, sa[8] = {0}, sq[4] = {0}, sp[4] = {0}, sg[4] = {0},
-         st3[3] = {0, 0, 0};
-  int nq = 0;
-  unsigned long long t0 = ~0ull, tend0 = 0, tend1 = 0;
-  int n1 = 0;
-  for (int w = 0; w < nwg; w++) {
-    const unsigned long long *r = &t[(size_t)w * PROF_SLOTS];
-    sL += (double)(r[4] - r[0]);
-    sM += (double)(r[1] - r[4]);
-    sS += (double)(r[2] - r[1]);
-    sW += (double)(r[3] - r[2]);
-    if (r[5]) { s1 += (double)(r[5] - r[0]); n1++; if (r[5] > tend1) tend1 = r[5]; }
-    for (int q = 0; q < 4; q++) sp[q] += (double)r[16 + q];
-    for (int q = 0; q < 4; q++) sg[q] += (double)r[20 + q];
-    if (r[14]) {  // quiet workgroup: M end | A* + barrier | predicate | phase Q + barrier
-      nq++;
-      sq[0] += (double)(r[6] - r[4]);
-      sq[1] += (double)(r[7] - r[6]);
-      sq[2] += (double)(r[8] - r[7]);
-      sq[3] += (double)(r[9] - r[8]);
-      if (r[10] && r[11]) {  // tail: rewards | cog | env_tail + outputs
-        st3[0] += (double)(r[10] - r[1]);
-        st3[1] += (double)(r[11] - r[10]);
-        st3[2] += (double)(r[2] - r[11]);
-      }
-    } else {
-      for (int a = 0; a < 8; a++)
-        if (r[6 + a]) sa[a] += (double)(r[6 + a] - (a ? r[5 + a] : r[1]));
-    }
-    if (r[0] < t0) t0 = r[0];
-    if (r[3] > tend0) tend0 = r[3];
-  }
-  const double us = 0.01;  // 100 MHz ticks
-  {  // spread of the per-workgroup phase-S spans (slot 1 -> 2)
-    std::vector<double> sv;
-    for (int w = 0; w < nwg; w++) {
-      const unsigned long long *r = &t[(size_t)w * PROF_SLOTS];
-      if (r[2] > r[1]) sv.push_back((double)(r[2] - r[1]) * 0.01);
-    }
-    {  // the slowest workgroup's parts (slots 16..23)
-      int wm = -1;
-      double best = -1;
-      for (int w = 0; w < nwg; w++) {
-        const unsigned long long *r = &t[(size_t)w * PROF_SLOTS];
-        if (r[2] > r[1] && (double)(r[2] - r[1]) > best) { best = (double)(r[2] - r[1]); wm = w; }
-      }
-      if (wm >= 0) {
-        const unsigned long long *r = &t[(size_t)wm * PROF_SLOTS];
-        fprintf(stderr, "[lnw prof] slowest workgroup %d: S %.1f us = take_action %.1f, LOS prefetch %.1f, get_obs %.1f "
-                        "(walk %.1f, observed %.1f, bearings %.1f, fix targets %.1f), reward %.1f\n",
-                wm, best * 0.01, r[16] * 0.01, r[17] * 0.01, r[18] * 0.01, r[20] * 0.01, r[21] * 0.01,
-                r[22] * 0.01, r[23] * 0.01, r[19] * 0.01);
-      }
-    }
-    std::sort(sv.begin(), sv.end());
-    if (!sv.empty())
-      fprintf(stderr, "[lnw prof] phase S span per workgroup: p10 %.1f, p50 %.1f, p90 %.1f, max %.1f us\n",
-              sv[sv.size() / 10], sv[sv.size() / 2], sv[sv.size() * 9 / 10], sv.back());
-  }
-  fprintf(stderr, "[lnw prof] wg=%d mean L %.2f us, M %.2f us, S %.2f us, W %.2f us, wave1 end-from-start %.2f us; "
-                  "grid: last wave0 end %.2f us, last wave1 end %.2f us after first start\n",
-          nwg, sL / nwg * us, sM / nwg * us, sS / nwg * us, sW / nwg * us, n1 ? s1 / n1 * us : 0.0,
-          (double)(tend0 - t0) * us, tend1 ? (double)(tend1 - t0) * us : 0.0);
-  {
-    double bs = 0, bm = 0, bl = 0;
-    for (int w = 0; w < nwg; w++) {
-      const unsigned long long *r = &t[(size_t)w * PROF_SLOTS];
-      bs += (double)r[24]; bm += (double)r[25]; bl += (double)r[26];
-    }
-    if (bl > 0)
-      fprintf(stderr, "[lnw prof] EW bearings (contact variant): %.0f evaluated, wave max summed %.0f, "
-                      "active lanes %.0f; balanced/actual %.3f\n",
-              bs, bm, bl, bs / 64.0 / bm);
-  }
-  {  // grid timeline: workgroup start (slot 0), stream / phase S start (slot 1),
-     // wave-1 end (slot 5), each as p10 / p50 / p90 / max after the first start
-    const int slots[3] = {0, 1, 5};
-    const char *names[3] = {"start", "S/stream start", "wave-1 end"};
-    for (int k = 0; k < 3; k++) {
-      std::vector<double> sv;
-      for (int w = 0; w < nwg; w++) {
-        const unsigned long long v = t[(size_t)w * PROF_SLOTS + slots[k]];
-        if (v >= t0) sv.push_back((double)(v - t0) * us);
-      }
-      std::sort(sv.begin(), sv.end());
-      if (!sv.empty())
-        fprintf(stderr, "[lnw prof] timeline %s: p10 %.2f, p50 %.2f, p90 %.2f, max %.2f us\n", names[k],
-                sv[sv.size() / 10], sv[sv.size() / 2], sv[sv.size() * 9 / 10], sv.back());
-    }
-  }
-  {  // wave-1 end (slot 5) per XCC: count, mean, max after the first start
-    double se[16] = {0}, mx[16] = {0};
-    int nx[16] = {0};
-    for (int w = 0; w < nwg; w++) {
-      const unsigned long long *r = &t[(size_t)w * PROF_SLOTS];
-      if (!r[5] || r[5] < t0) continue;
-      const int x = (int)(r[30] & 15);
-      const double e = (double)(r[5] - t0) * us;
-      se[x] += e; nx[x]++;
-      if (e > mx[x]) mx[x] = e;
-    }
-    {  // per CU (XCC, SE, SH, CU from HW_ID bits 15:8): spread of CU means vs within-CU spread
-      std::vector<std::pair<int, double>> v;
-      for (int w = 0; w < nwg; w++) {
-        const unsigned long long *r = &t[(size_t)w * PROF_SLOTS];
-        if (!r[5] || r[5] < t0) continue;
-        v.push_back({(int)((r[30] & 15) << 8 | ((r[31] >> 8) & 0xff)), (double)(r[5] - t0) * us});
-      }
-      std::sort(v.begin(), v.end());
-      std::vector<double> means, spans;
-      for (size_t i = 0; i < v.size();) {
-        size_t j = i;
-        double sm = 0, lo = 1e30, hi = -1e30;
-        while (j < v.size() && v[j].first == v[i].first) { sm += v[j].second; lo = std::min(lo, v[j].second); hi = std::max(hi, v[j].second); j++; }
-        means.push_back(sm / (double)(j - i));
-        spans.push_back(hi - lo);
-        i = j;
-      }
-      std::sort(means.begin(), means.end());
-      std::sort(spans.begin(), spans.end());
-      if (!means.empty())
-        fprintf(stderr, "[lnw prof] CUs %zu: CU-mean wave-1 end p10 %.1f p50 %.1f p90 %.1f max %.1f; within-CU span p50 %.1f p90 %.1f max %.1f us\n",
-                means.size(), means[means.size() / 10], means[means.size() / 2], means[means.size() * 9 / 10], means.back(),
-                spans[spans.size() / 2], spans[spans.size() * 9 / 10], spans.back());
-    }
-    {  // SIMD placement: wave 0 (phase S) sharing its SIMD with another workgroup's wave 0
-      std::vector<int> key(nwg);
-      for (int w = 0; w < nwg; w++) {
-        const unsigned long long *r = &t[(size_t)w * PROF_SLOTS];
-        key[w] = (int)((r[30] & 15) << 12 | ((r[31] >> 8) & 0xff) << 4 | ((r[31] >> 4) & 3));
-      }
-      std::vector<int> sk = key;
-      std::sort(sk.begin(), sk.end());
-      double e0[2] = {0, 0}, m0[2] = {0, 0};
-      int n0[2] = {0, 0}, same = 0;
-      for (int w = 0; w < nwg; w++) {
-        const unsigned long long *r = &t[(size_t)w * PROF_SLOTS];
-        const int cnt = (int)(std::upper_bound(sk.begin(), sk.end(), key[w]) - std::lower_bound(sk.begin(), sk.end(), key[w]));
-        const int k = cnt > 1 ? 1 : 0;
-        if (r[3] < t0) continue;
-        const double e = (double)(r[3] - t0) * us;
-        e0[k] += e; n0[k]++;
-        if (e > m0[k]) m0[k] = e;
-        same += ((r[31] >> 4) & 3) == ((r[29] >> 4) & 3);
-      }
-      fprintf(stderr, "[lnw prof] wave-0 SIMD: alone %d (end mean %.1f max %.1f us), shared %d (mean %.1f max %.1f us); "
-                      "waves 0/1 on one SIMD in %d workgroups\n",
-              n0[0], n0[0] ? e0[0] / n0[0] : 0.0, m0[0], n0[1], n0[1] ? e0[1] / n0[1] : 0.0, m0[1], same);
-    }
-    fprintf(stderr, "[lnw prof] wave-1 end by XCC (n/mean/max us):");
-    for (int x = 0; x < 16; x++)
-      if (nx[x]) fprintf(stderr, " %d:%d/%.1f/%.1f", x, nx[x], se[x] / nx[x], mx[x]);
-    fprintf(stderr, "; block%%8==xcc for %d of %d\n",
-            [&] { int k = 0; for (int w = 0; w < nwg; w++) k += (int)(t[(size_t)w * PROF_SLOTS + 30] & 15) == (w & 7); return k; }(), nwg);
-  }
-  {
-    double rq = 0;
-    int nr2 = 0;
-    for (int w = 0; w < nwg; w++) {
-      const unsigned long long *r = &t[(size_t)w * PROF_SLOTS];
-      if (r[14] && r[12] > r[8] && r[8]) { rq += (double)(r[12] - r[8]); nr2++; }
-    }
-    if (nr2) fprintf(stderr, "[lnw prof] repeated quiet test (diagnostics): %.2f us\n", rq / nr2 * us);
-  }
-  {  // quiet small workgroups (direct mode): each wave's phase-Q work from the
-     // test's end (slots 27 / 15), wave 1's rows staged (28) and stored (5)
-     // from the barrier (9)
-    double q0 = 0, q1 = 0, rb = 0, rc = 0;
-    int nd = 0;
-    for (int w = 0; w < nwg; w++) {
-      const unsigned long long *r = &t[(size_t)w * PROF_SLOTS];
-      if (!r[14] || !r[28] || !r[15] || !r[27] || r[28] < r[9]) continue;
-      nd++;
-      q0 += (double)(r[27] - r[8]);
-      q1 += (double)(r[15] - r[8]);
-      rb += (double)(r[28] - r[9]);
-      rc += (double)(r[5] - r[28]);
-    }
-    if (nd)
-      fprintf(stderr, "[lnw prof] quiet direct %d: phase-Q work wave 0 %.2f, wave 1 %.2f us; after the barrier "
-                      "rows staged %.2f, stored %.2f us\n",
-              nd, q0 / nd * us, q1 / nd * us, rb / nd * us, rc / nd * us);
-  }
-#ifdef LNW_DIAG
-  {  // quiet workgroups: the kernel's first instruction (slot 13) to stamp 0, and stamp 0 to phase L's end
-    double se = 0, sl = 0, me = 0;
-    int ne = 0;
-    for (int w = 0; w < nwg; w++) {
-      const unsigned long long *r = &t[(size_t)w * PROF_SLOTS];
-      if (!r[14] || !r[13] || r[13] > r[0]) continue;
-      ne++;
-      se += (double)(r[0] - r[13]);
-      sl += (double)(r[4] - r[0]);
-      if ((double)(r[0] - r[13]) > me) me = (double)(r[0] - r[13]);
-    }
-    if (ne)
-      fprintf(stderr, "[lnw prof] entry -> stamp 0 %.3f us (max %.2f), stamp 0 -> phase-L end %.3f us (%d quiet records)\n",
-              se / ne * us, me * us, sl / ne * us, ne);
-  }
-#endif
-  if (nq)
-    fprintf(stderr, "[lnw prof] quiet workgroups %d: M %.2f us, A*+barrier %.2f us, quiet test %.2f us, Q+barrier %.2f us; "
-                    "tail: rewards %.2f, cog %.2f, env_tail+outputs %.2f us\n",
-            nq, sq[0] / nq * us, sq[1] / nq * us, sq[2] / nq * us, sq[3] / nq * us, st3[0] / nq * us,
-            st3[1] / nq * us, st3[2] / nq * us);
-  const int ns = nwg - nq;
-  fprintf(stderr, "[lnw prof] phase S workgroups %d, per agent (us):", ns);
-  for (int a = 0; a < 8; a++) fprintf(stderr, " %.2f", ns ? sa[a] / ns * us : 0.0);
-  fprintf(stderr, "; section totals take_action %.2f, LOS prefetch %.2f, get_obs %.2f, reward %.2f us\n",
-          ns ? sp[0] / ns * us : 0.0, ns ? sp[1] / ns * us : 0.0, ns ? sp[2] / ns * us : 0.0,
-          ns ? sp[3] / ns * us : 0.0);
-  fprintf(stderr, "[lnw prof] get_obs parts (templated): pair walk %.2f, observed stores %.2f, bearings+fixes %.2f, fix targets %.2f us\n",
-          ns ? sg[0] / ns * us : 0.0, ns ? sg[1] / ns * us : 0.0, ns ? sg[2] / ns * us : 0.0,
-          ns ? sg[3] / ns * us : 0.0);
-}
 
 extern "C" {
 
@@ -493,9 +407,9 @@ int lnw_create(const lnw_params *params, int32_t n_envs, int32_t nb, int32_t nr,
   if (nb < 1 || nr < 1 || nb > 16 || nr > 16)
     return fail(LNW_EUNSUPPORTED, "need 1 <= nb, nr <= 16 ships per side");
   HIPCHK(hipSetDevice(device));
-  lnw_handle *h = new lnw_handle();
+  lnw_handle *h = new lnw_handle();  // (reads the environment knobs)
   h->device = device;
-  if (const char *dbg = getenv("LNW_DEBUG_SKIP")) h->dbg_skip = atoi(dbg);
+  const Knobs &kn = h->knobs;
 #ifndef LNW_DIAG
   // the shipped library honours only the knobs that change the launch shape or
   // code path, never the results (bit 9: no quiet path, 15: the group kernel's
@@ -505,32 +419,21 @@ int lnw_create(const lnw_params *params, int32_t n_envs, int32_t nb, int32_t nr,
   // replaced arithmetic exist only in the diagnostics build (-DLNW_DIAG,
   // lnw.build.build_diag)
   constexpr int kResultPreserving = 512 | 32768 | 131072 | 4194304 | 8388608 | (1 << 28) | (1 << 29);
-  if (h->dbg_skip & ~kResultPreserving) {
-    const int bad = h->dbg_skip & ~kResultPreserving;
+  if (kn.dbg_skip & ~kResultPreserving) {
+    const int bad = kn.dbg_skip & ~kResultPreserving;
     delete h;
     return fail(LNW_EINVAL, "LNW_DEBUG_SKIP bits " + std::to_string(bad) +
                                 " change results; they exist only in the diagnostics build (-DLNW_DIAG)");
   }
 #endif
-  h->prof = getenv("LNW_PROF") != nullptr;
-  h->force_generic = getenv("LNW_FORCE_GENERIC") != nullptr;
-  // LNW_NO_GROUP: runtime team sizes on the one-lane-per-env kernel (A/B tests)
-  h->no_group = getenv("LNW_NO_GROUP") != nullptr;
-  h->force_group = getenv("LNW_FORCE_GROUP") != nullptr;
-  h->no_split_rows = getenv("LNW_NO_SPLIT_ROWS") != nullptr;
-  // LNW_NO_UNITS: one 64-env unit per workgroup for the headline shape (A/B tests)
-  h->no_units = getenv("LNW_NO_UNITS") != nullptr;
-  h->no_slab = getenv("LNW_NO_SLAB") != nullptr;
-  h->kp.xcd_remap = getenv("LNW_NO_XCD_REMAP") == nullptr ? 1 : 0;
-  // LNW_GROUP_MARCH=1: the group kernel marches its pair LOS over the LDS
-  // terrain mask instead of loading LOS-table words (A/B)
-  h->kp.group_march = getenv("LNW_GROUP_MARCH") != nullptr ? 1 : 0;
+  h->kp.xcd_remap = kn.no_xcd_remap ? 0 : 1;
+  h->kp.group_march = kn.group_march ? 1 : 0;
   // write-through observation stores (st_obs4) while a side's output fits the
-  // 32-bit buffer offsets; LNW_NO_STORE_WT keeps non-temporal stores (A/B)
+  // 32-bit buffer offsets
   {
     const int ns = nb > nr ? nb : nr;
     const double side_bytes = (double)n_envs * ns * (4 * ns + 52) * 4.0;
-    h->store_wt = getenv("LNW_NO_STORE_WT") == nullptr && side_bytes < 2147483648.0;
+    h->store_wt = !kn.no_store_wt && side_bytes < 2147483648.0;
   }
   h->params = *params;
   h->E = n_envs; h->nb = nb; h->nr = nr; h->A = nb + nr;
@@ -676,11 +579,7 @@ int lnw_load_terrain(lnw_handle *h, const uint8_t *grid_host, int32_t G) {
   long long nl = (long long)G * G * LOS_W;
   const int mwords = G * h->W16 * 4 <= 64 * 1024 ? G * h->W16 : 0;  // terrain mask staged in LDS
   {  // a few resident rounds of workgroups, each looping over its items
-    int ncu = 256;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, h->device) == hipSuccess && prop.multiProcessorCount > 0)
-      ncu = prop.multiProcessorCount;
-    const long long need = (nl + 255) / 256, cap = (long long)ncu * 8;
+    const long long need = (nl + 255) / 256, cap = (long long)device_ncu(h->device) * 8;
     build_los_table_kernel<<<(unsigned)(need < cap ? need : cap), 256, (size_t)mwords * 4>>>(
         h->d_mask2, G, h->W16, h->d_lostab, mwords);
   }
@@ -693,10 +592,12 @@ int lnw_load_terrain(lnw_handle *h, const uint8_t *grid_host, int32_t G) {
     const size_t need = step_launch_lds_bytes(h, WAVE / h->nb);
     // the same bound the launch attribute below grants
     if (need > (size_t)GROUP_LDS_MAX) return fail(LNW_EUNSUPPORTED, "agent count needs more LDS than a CU has");
-    const LdsLayout GLy = lds_layout(h->A, h->nb, h->nr, h->nmax, h->G * h->W16, h->G);
-    const size_t gneed = (size_t)group_lds(GLy, h->G * h->W16, h->A, h->nb * h->nr, h->kp.atan_odd != 0).total + 1024;
+    // the group kernel's LDS, fixed from here on (plan_step reads it)
+    h->group_lds = group_lds(lds_layout(h->A, h->nb, h->nr, h->nmax, h->G * h->W16, h->G), h->G * h->W16, h->A,
+                             h->nb * h->nr, h->kp.atan_odd != 0);
+    const size_t gneed = (size_t)h->group_lds.total + 1024;
     // (else runtime sizes stay on step_kernel<0, 0>)
-    h->group_fits = group_lds(GLy, h->G * h->W16, h->A, h->nb * h->nr, h->kp.atan_odd != 0).ms >= 0;
+    h->group_fits = h->group_lds.ms >= 0;
     // the limit is per kernel function and device, shared by every handle of
     // the process on that device: set to GROUP_LDS_MAX once per device, so a
     // smaller handle never lowers it under a larger one's launch (the launch's
@@ -706,21 +607,10 @@ int lnw_load_terrain(lnw_handle *h, const uint8_t *grid_host, int32_t G) {
     const size_t uneed = (size_t)UNITS * ((step_lds_bytes(h) + 15) & ~(size_t)15);
     h->units_fit = uneed <= (size_t)UNITS_LDS_MAX;
     if (!(lds_opt_in & dbit) && (need > 64 * 1024 || gneed > 64 * 1024 || uneed > 64 * 1024)) {
-      HIPCHK(hipFuncSetAttribute((const void *)step_kernel<4, 4, false, false, 1, false, true>,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, GROUP_LDS_MAX));
-      const void *ks[17] = {(const void *)step_kernel<4, 4, true, false, 1, true>,
-                            (const void *)step_kernel<0, 0>,       (const void *)step_kernel<2, 2>,
-                            (const void *)step_kernel<3, 3>,       (const void *)step_kernel<4, 4>,
-                            (const void *)step_kernel<2, 2, true>, (const void *)step_kernel<3, 3, true>,
-                            (const void *)step_kernel<4, 4, true>, (const void *)step_kernel<0, 0, false, true>,
-                            (const void *)observe_kernel<0, 0, false>, (const void *)step_group_kernel,
-                            (const void *)observe_kernel<2, 2, false>, (const void *)observe_kernel<3, 3, false>,
-                            (const void *)observe_kernel<4, 4, false>, (const void *)observe_kernel<2, 2, true>,
-                            (const void *)observe_kernel<3, 3, true>, (const void *)observe_kernel<4, 4, true>};
-      for (const void *kk : ks)
-        HIPCHK(hipFuncSetAttribute(kk, hipFuncAttributeMaxDynamicSharedMemorySize, GROUP_LDS_MAX));
-      HIPCHK(hipFuncSetAttribute((const void *)step_kernel<4, 4, false, false, UNITS>,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, UNITS_LDS_MAX));
+      for (const auto &row : STEP_KERNELS)
+        HIPCHK(hipFuncSetAttribute((const void *)row.fn, hipFuncAttributeMaxDynamicSharedMemorySize, row.lds_cap));
+      for (const auto &row : OBS_KERNELS)
+        HIPCHK(hipFuncSetAttribute((const void *)row.fn, hipFuncAttributeMaxDynamicSharedMemorySize, row.lds_cap));
       lds_opt_in |= dbit;
     }
   }
@@ -808,11 +698,10 @@ int lnw_reset(lnw_handle *h, const uint8_t *env_mask_dev, const lnw_spawn *spawn
   return 0;
 }
 
-namespace {
-// lnw_step's launch (lnw_step_seq makes one per step)
-int step_launch(lnw_handle *h, void *actions_dev, int32_t action_dtype,
-                const uint8_t *row_kind_dev, float *obs_blue_dev, float *obs_red_dev, float *rew_blue_dev,
-                float *rew_red_dev, int32_t *done_dev, float *cog_dev, void *stream) {
+// One step launch (lnw_step_seq makes one per step)
+int lnw_step(lnw_handle *h, void *actions_dev, int32_t action_dtype, const uint8_t *row_kind_dev,
+             float *obs_blue_dev, float *obs_red_dev, float *rew_blue_dev, float *rew_red_dev,
+             int32_t *done_dev, float *cog_dev, void *stream) {
   if (!h || !actions_dev) return fail(LNW_EINVAL, "null argument");
   if (!h->terrain) return fail(LNW_ESTATE, "lnw_load_terrain must be called first");
   if (action_dtype != LNW_ACT_F32 && action_dtype != LNW_ACT_F64 && action_dtype != LNW_ACT_I32)
@@ -826,27 +715,15 @@ int step_launch(lnw_handle *h, void *actions_dev, int32_t action_dtype,
   KParams k = h->kp;
   k.act_dtype = action_dtype;
   k.no_obs = obs_blue_dev == nullptr ? 1 : 0;
-  k.dbg_skip = h->dbg_skip;
+  k.dbg_skip = h->knobs.dbg_skip;
   k.store_wt = h->store_wt;
   KState s;
   if (int rc = launch_state(h, s)) return rc;
-  k.qdirect = step_qdirect(h, k.epw) ? 1 : 0;
-  size_t lds = step_launch_lds_bytes(h, k.epw);
-  dim3 grid((h->E + k.epw - 1) / k.epw), block(WAVE);
+  const StepPlan p = plan_step(h, k.epw, k.no_obs != 0);
+  k.qdirect = p.qdirect ? 1 : 0;
   hipStream_t st = (hipStream_t)stream;
-  // (medium ships: 5x5 windows and shorter rows, the runtime-size kernels only)
-  bool generic = h->force_generic;
-  const bool templated = k.los_mode != 2 && !generic && !h->has_medium && h->nb == h->nr && h->nb >= 2 && h->nb <= 4 &&
-                         !(h->force_group && h->group_fits);
-  const bool use_group = k.los_mode != 2 && !templated && !generic && !h->no_group && h->group_fits;
-  // 4v4 at 64 envs per workgroup in LOS-table mode, whole units (the headline):
-  // the units kernel (LNW_NO_UNITS keeps one unit per workgroup)
-  const bool units = templated && h->nb == 4 && !h->contact && !h->no_units && h->units_fit && k.epw == EPW &&
-                     k.los_mode == 0 && h->E % (EPW * UNITS) == 0 && !(h->dbg_skip & (1 | 2 | 512));
-  // per-unit records (LNW_PROF) of the kernel launched below (the group kernel has its own grid)
-  const unsigned nwg = use_group ? (unsigned)((h->E + GEPW - 1) / GEPW) : grid.x;
-  if (h->prof) {
-    const size_t slots = (size_t)nwg * PROF_SLOTS;
+  if (h->knobs.prof) {
+    const size_t slots = (size_t)p.nwg * PROF_SLOTS;
     if (slots > h->prof_cap) {
       HIPCHK(hipStreamSynchronize(st));
       if (h->d_prof) { (void)hipFree(h->d_prof); h->d_prof = nullptr; h->prof_cap = 0; }
@@ -855,63 +732,18 @@ int step_launch(lnw_handle *h, void *actions_dev, int32_t action_dtype,
     }
     HIPCHK(hipMemsetAsync(h->d_prof, 0, slots * sizeof(unsigned long long), st));
     s.prof = h->d_prof;
-  }
-#define LNW_STEP(NB_, NR_, CW_, RW_)                                                             \
-  step_kernel<NB_, NR_, CW_, RW_><<<grid, dim3(NB_ > 0 && EPW == WAVE ? 2 * WAVE : WAVE), lds, st>>>(k, s, actions_dev, row_kind_dev, obs_blue_dev, \
-                                                 obs_red_dev, rew_blue_dev, rew_red_dev,        \
-                                                 done_dev, cog_dev)
-  const bool cw = h->contact;
-  h->last_kernel = units ? LNW_KERNEL_UNITS
-                   : k.los_mode == 2 ? LNW_KERNEL_REFLOS
-                   : templated ? (cw ? LNW_KERNEL_TEAM_CONTACT : LNW_KERNEL_TEAM)
-                   : use_group ? LNW_KERNEL_GROUP : LNW_KERNEL_GENERIC;
-  if (units) {
-    // 4 units of 64 envs per workgroup, one workgroup per CU (step_kernel UN)
-    step_kernel<4, 4, false, false, UNITS><<<dim3(h->E / (EPW * UNITS)), dim3(2 * WAVE * UNITS),
-                                             (size_t)UNITS * ((lds + 15) & ~(size_t)15), st>>>(
-        k, s, actions_dev, row_kind_dev, obs_blue_dev, obs_red_dev, rew_blue_dev, rew_red_dev, done_dev,
-        cog_dev);
-  }
-  else if (k.los_mode == 2) LNW_STEP(0, 0, false, true);  // diagnostics: the reference's LOS work
-  else if (templated && h->nb == 4) {
-    // the contact variant: phase S split by side (step_kernel PS; LNW_NO_SPLIT_ROWS:
-    // only for steps without rows, A/B)
-    if (cw && k.los_mode == 0 && (k.no_obs || !h->no_split_rows))
-      step_kernel<4, 4, true, false, 1, true><<<grid, dim3(2 * WAVE), lds, st>>>(
-          k, s, actions_dev, row_kind_dev, obs_blue_dev, obs_red_dev, rew_blue_dev, rew_red_dev, done_dev, cog_dev);
-    else if (cw) LNW_STEP(4, 4, true, false);
-    else if (k.qdirect && k.epw * 4 > WAVE)  // two-slab direct rows (step_qdirect)
-      step_kernel<4, 4, false, false, 1, false, true><<<grid, dim3(2 * WAVE), lds, st>>>(
-          k, s, actions_dev, row_kind_dev, obs_blue_dev, obs_red_dev, rew_blue_dev, rew_red_dev, done_dev, cog_dev);
-    else LNW_STEP(4, 4, false, false);
-  }
-  else if (templated && h->nb == 3) { if (cw) LNW_STEP(3, 3, true, false); else LNW_STEP(3, 3, false, false); }
-  else if (templated && h->nb == 2) { if (cw) LNW_STEP(2, 2, true, false); else LNW_STEP(2, 2, false, false); }
-  else if (use_group) {
-    // runtime team sizes: GL lanes per env (lnw_group.inc)
-    const GroupLds gl = group_lds(lds_layout(h->A, h->nb, h->nr, h->nmax, h->G * h->W16, h->G), h->G * h->W16,
-                                  h->A, h->nb * h->nr, k.atan_odd != 0);
-    const size_t glds = (size_t)gl.total;
-    if (s.prof)
+    if (p.row->code == LNW_KERNEL_GROUP) {
+      const GroupLds &gl = h->group_lds;
       fprintf(stderr, "[lnw prof] group kernel LDS %zu B (staged: target lists %d, dist_lz %d, bearing half table %d, pooled slopes %d)\n",
-              glds, (int)(gl.tls >= 0), (int)(gl.dlz >= 0), (int)(gl.atab >= 0), (int)(gl.ms >= 0));
-    step_group_kernel<<<dim3((h->E + GEPW - 1) / GEPW), dim3(GEPW * GL), glds, st>>>(
-        k, s, actions_dev, row_kind_dev, obs_blue_dev, obs_red_dev, rew_blue_dev, rew_red_dev,
-        done_dev, cog_dev);
+              p.lds, (int)(gl.tls >= 0), (int)(gl.dlz >= 0), (int)(gl.atab >= 0), (int)(gl.ms >= 0));
+    }
   }
-  else LNW_STEP(0, 0, false, false);
-#undef LNW_STEP
+  h->last_kernel = p.row->code;
+  p.row->fn<<<dim3(p.grid), dim3(p.block), p.lds, st>>>(k, s, actions_dev, row_kind_dev, obs_blue_dev, obs_red_dev,
+                                                         rew_blue_dev, rew_red_dev, done_dev, cog_dev);
   HIPCHK(hipGetLastError());
-  if (s.prof) prof_report(h, st, (int)nwg);
+  if (s.prof) prof_report(h->d_prof, st, (int)p.nwg);
   return 0;
-}
-}  // namespace
-
-int lnw_step(lnw_handle *h, void *actions_dev, int32_t action_dtype, const uint8_t *row_kind_dev,
-             float *obs_blue_dev, float *obs_red_dev, float *rew_blue_dev, float *rew_red_dev,
-             int32_t *done_dev, float *cog_dev, void *stream) {
-  return step_launch(h, actions_dev, action_dtype, row_kind_dev, obs_blue_dev, obs_red_dev, rew_blue_dev,
-                     rew_red_dev, done_dev, cog_dev, stream);
 }
 
 int lnw_step_seq(lnw_handle *h, const lnw_seq *seq, void *actions_dev, int32_t action_dtype,
@@ -930,14 +762,14 @@ int lnw_step_seq(lnw_handle *h, const lnw_seq *seq, void *actions_dev, int32_t a
     auto adv = [&](const void *p, long long stride, long long sz) {
       return p ? (void *)((char *)p + (long long)k * stride * sz) : nullptr;
     };
-    if (int e = step_launch(h, adv(actions_dev, seq->act_step, asz), action_dtype,
-                            (const uint8_t *)adv(row_kind_dev, seq->kind_step, 1),
-                            (float *)adv(obs_blue_dev, seq->obs_blue_step, 4),
-                            (float *)adv(obs_red_dev, seq->obs_red_step, 4),
-                            (float *)adv(rew_blue_dev, seq->rew_blue_step, rsz),
-                            (float *)adv(rew_red_dev, seq->rew_red_step, rsz),
-                            (int32_t *)adv(done_dev, seq->done_step, 4), (float *)adv(cog_dev, seq->cog_step, rsz),
-                            stream))
+    if (int e = lnw_step(h, adv(actions_dev, seq->act_step, asz), action_dtype,
+                         (const uint8_t *)adv(row_kind_dev, seq->kind_step, 1),
+                         (float *)adv(obs_blue_dev, seq->obs_blue_step, 4),
+                         (float *)adv(obs_red_dev, seq->obs_red_step, 4),
+                         (float *)adv(rew_blue_dev, seq->rew_blue_step, rsz),
+                         (float *)adv(rew_red_dev, seq->rew_red_step, rsz),
+                         (int32_t *)adv(done_dev, seq->done_step, 4), (float *)adv(cog_dev, seq->cog_step, rsz),
+                         stream))
       return e;
   }
   return 0;
@@ -959,22 +791,11 @@ int lnw_observe_ex(lnw_handle *h, int32_t agent, float *obs_blue_dev, int64_t bl
   if (((uintptr_t)obs_blue_dev | (uintptr_t)obs_red_dev) & 15) return fail(LNW_EINVAL, "rows must be 16-B aligned");
   KState s;
   if (int rc = launch_state(h, s)) return rc;
-  size_t lds = step_lds_bytes(h);
-  dim3 grid((h->E + h->kp.epw - 1) / h->kp.epw), block(WAVE);
-  hipStream_t st = (hipStream_t)stream;
-  const bool tmpl = !h->force_generic && !h->has_medium && h->params.los_mode != 2 && h->nb == h->nr;
-  const bool cw = h->contact;
+  const ObsPlan p = plan_observe(h);
   KParams k = h->kp;
   k.obs_stride[0] = blue_env_stride;
   k.obs_stride[1] = red_env_stride;
-#define LNW_OBS(NB_, CW_)                                                                          \
-  observe_kernel<NB_, NB_, CW_><<<grid, dim3(NB_ > 0 && CW_ ? 2 * WAVE : WAVE), lds, st>>>(k, s, agent, \
-                                                                                    obs_blue_dev, obs_red_dev)
-  if (tmpl && h->nb == 4) { if (cw) LNW_OBS(4, true); else LNW_OBS(4, false); }
-  else if (tmpl && h->nb == 3) { if (cw) LNW_OBS(3, true); else LNW_OBS(3, false); }
-  else if (tmpl && h->nb == 2) { if (cw) LNW_OBS(2, true); else LNW_OBS(2, false); }
-  else LNW_OBS(0, false);
-#undef LNW_OBS
+  p.row->fn<<<dim3(p.grid), dim3(p.block), p.lds, (hipStream_t)stream>>>(k, s, agent, obs_blue_dev, obs_red_dev);
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -3472,4 +3472,5 @@ __global__ void reset_kernel(KParams P, KState S, const uint8_t *mask) {
 
 #include "lnw_tables.inc"
 
+#include "lnw_prof.inc"
 #include "lnw_host.inc"
