@@ -532,6 +532,71 @@ int lnw_qnet_grad(const lnw_qlearn_args *args, void *stream);
 int lnw_qnet_adam(float *params, const float *grad, float *m, float *v, int64_t count, int64_t *step_dev,
                   float lr, float beta1, float beta2, float eps, float clamp, void *stream);
 
+/* ---- MAPPO learner step ------------------------------------------------------
+ * lnw_ppo_grad is one minibatch update of the reference's PPO.learn
+ * (ppo.py:321-390) for the blue side on `rows` rows, up to the two gradients.
+ * Row r is observation row ri = row_index ? row_index[r] : r of obs
+ * [groups][n][D]; its global state is the n * D floats of group ri / n.
+ *   evaluate (ppo.py:673-693): the actor on each row with that row's own
+ *     BatchNorm statistics (the reference calls it one state at a time in
+ *     train()), new_log_probs and entropies [rows][4]; V = critic(global state);
+ *   advantage: PPO.gae over the rows as the sequence (gamma, lambda), + V, then
+ *     popart_normalize against rtg (unbiased std; std = 0 gives NaN), in double;
+ *   actor_loss = -(mean(min(adv ratio, adv clamp(ratio, 1 -+ eps_clip))) +
+ *     entropy_coef mean(entropies)); critic_loss = sqrt(mean(max((v - rtg)^2,
+ *     (clamp(v, v_old -+ eps_clip) - rtg)^2))); torch's tie and clamp gradient
+ *     rules (an in-range element passes the whole gradient);
+ *   both gradients, unclipped, in the flat layouts below. Max pool sends the
+ *     gradient to the first maximum in row-major order.
+ * The actor's running statistics take the `rows` sequential updates of the
+ * reference (momentum 0.1, unbiased variance, minibatch order) in actor_params
+ * unless freeze_running.
+ * Actor layout (floats): conv1 w 45, b 5; norm1 w, b, running mean, var 5 each;
+ * conv2 w 360, b 8; norm2 w, b, running mean, var 8 each; convhead w 96, b 12;
+ * layernorm w, b [n_in] each (BatchedActor.packed_features(), n_in = D - 37);
+ * fc1 w [64][n_in], b 64; fc2 w [64][64], b 64; fc3 w [32][64], b 32;
+ * normal_head w [4][32]; log_std_head w [4][32]; logstd 1 (gradient 0).
+ * Critic layout: the state_dict order, fc1 w [32][n D], b 32; fc2 w [64][32],
+ * b 64; fc3 w [64][64], b 64; fc4 w [64], b 1.
+ * A chain of launches on `stream`: no host synchronisation, no allocation, no
+ * atomics; bitwise reproducible. workspace: lnw_ppolearn_workspace_bytes(rows,
+ * n, D) bytes, 16-B aligned (0 for unsupported shapes). Limits as
+ * lnw_policy_act: 16-B aligned rows, D % 4 == 0, 49 <= D, D - 37 <= 64; n <= 16.
+ *
+ * lnw_ppo_clip_adam is clip_grad_norm_(max_norm) followed by lnw_qnet_adam's
+ * Adam step: the global L2 norm of grad (fixed order, double), every gradient
+ * multiplied by min(1, max_norm / (norm + 1e-6)) from a device scalar.
+ * scale_norm [2] receives that factor and the norm. */
+typedef struct lnw_ppolearn_args {
+  const float *obs;            /* [groups][n][D], 16-B aligned */
+  const int64_t *row_index;    /* NULL (identity), or [rows] rows of obs */
+  int64_t rows;
+  int32_t n, D;
+  const float *actions;        /* [rows][4] */
+  const float *old_log_probs;  /* [rows][4] */
+  const float *rtg;            /* [rows] */
+  const float *old_values;     /* [rows] */
+  float eps_clip, entropy_coef, gamma, lambda_;
+  int32_t freeze_running;
+  float *actor_params;         /* running statistics updated in place */
+  const float *critic_params;
+  float *actor_grad;           /* [579 + 2 n_in + 64 n_in + 64 + 4160 + 2080 + 256] out */
+  float *critic_grad;          /* [32 n D + 32 + 2112 + 4160 + 65] out */
+  float *actor_loss;           /* [1] out */
+  float *critic_loss;          /* [1] out */
+  float *new_log_probs;        /* NULL, or [rows][4] */
+  float *entropies;            /* NULL, or [rows][4] */
+  float *values;               /* NULL, or [rows] */
+  float *advantage;            /* NULL, or [rows] */
+  void *workspace;
+  int64_t workspace_bytes;
+} lnw_ppolearn_args;
+int64_t lnw_ppolearn_workspace_bytes(int64_t rows, int32_t n, int32_t D);
+int lnw_ppo_grad(const lnw_ppolearn_args *args, void *stream);
+int lnw_ppo_clip_adam(float *params, const float *grad, float *m, float *v, int64_t count, int64_t *step_dev,
+                      float lr, float beta1, float beta2, float eps, float max_norm, float *scale_norm,
+                      void *stream);
+
 /* Host-side constants the kernels use (for tests): hit probability tables
  * 1-(1-p)^n for p in {0.45, 0.63}, n = 0..8, in float64 and float32. */
 int lnw_hit_tables(double *tab64 /* [2][9] */, float *tab32 /* [2][9] */);

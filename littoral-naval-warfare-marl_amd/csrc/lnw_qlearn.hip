@@ -48,6 +48,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #include "lnw_convhead.inc"
 #include "lnw_qhead.inc"
+#include "lnw_adam.inc"
 
 constexpr int QL_THREADS = 128;  // rows per workgroup
 constexpr int QL_WAVES = QL_THREADS / WAVE;
@@ -726,28 +727,15 @@ __global__ __launch_bounds__(WAVE) void ql_stats_kernel(lnw_qlearn_args a, Ws w)
   P[V + c] = mom * unb + (1.0f - mom) * P[V + c];
 }
 
-// ---- Adam (torch.optim.Adam's single-tensor arithmetic), gradient clamped first -----------
-// The hyperparameters arrive as the doubles the caller meant (as_decimal): torch
-// forms 1 - beta, lr / (1 - beta1^t) and sqrt(1 - beta2^t) in double and rounds
-// each to float32 once.
+// ---- Adam (adam_apply: lnw_adam.inc), gradient clamped first ---------------------------------
 __global__ __launch_bounds__(256) void ql_adam_kernel(float *p, const float *g, float *m, float *v, long long count,
                                                       const long long *step_dev, double lr, double beta1,
                                                       double beta2, double eps, float clamp) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= count) return;
-  const double t = (double)(*step_dev + 1);
-  const double bc1 = 1.0 - pow(beta1, t), bc2 = 1.0 - pow(beta2, t);
-  const float nstep = (float)(-(lr / bc1));
-  const float bc2s = (float)sqrt(bc2);
-  const float w1 = (float)(1.0 - beta1), w2 = (float)(1.0 - beta2), b2 = (float)beta2, epsf = (float)eps;
   float gi = g[i];
   if (clamp > 0.f) gi = fminf(fmaxf(gi, -clamp), clamp);
-  const float mi = m[i] + w1 * (gi - m[i]);
-  const float vi = v[i] * b2 + (w2 * gi) * gi;
-  const float denom = sqrtf(vi) / bc2s + epsf;
-  m[i] = mi;
-  v[i] = vi;
-  p[i] = p[i] + (nstep * mi) / denom;
+  adam_apply(p, m, v, i, gi, step_dev, lr, beta1, beta2, eps);
 }
 
 __global__ void ql_advance_kernel(long long *step_dev) { *step_dev += 1; }
@@ -755,17 +743,6 @@ __global__ void ql_advance_kernel(long long *step_dev) { *step_dev += 1; }
 int slab_width(int n_in) {
   const int head = Q_OUT * n_in + Q_OUT;
   return ((head > SLAB_MIN ? head : SLAB_MIN) + 3) & ~3;
-}
-
-// The double a float argument was before the ABI narrowed it: the shortest
-// decimal that rounds to the float (0.9f -> 0.9, 1e-4f -> 1e-4), else the float.
-double as_decimal(float x) {
-  char buf[32];
-  for (int digits = 1; digits <= 9; digits++) {
-    snprintf(buf, sizeof buf, "%.*g", digits, (double)x);
-    if (strtof(buf, nullptr) == x) return strtod(buf, nullptr);
-  }
-  return (double)x;
 }
 
 }  // namespace

@@ -15,4 +15,7 @@ def __getattr__(name):
     if name == "BatchedGame":
         from .batched import BatchedGame
         return BatchedGame
+    if name == "PPOLearner":
+        from .ppolearn import PPOLearner
+        return PPOLearner
     raise AttributeError(name)

@@ -33,6 +33,7 @@ SYMBOLS = [
     "lnw_state_bytes", "lnw_get_state", "lnw_set_state", "lnw_step_kernel",
     "lnw_policy_act", "lnw_rollout_post", "lnw_qnet_act",
     "lnw_qlearn_workspace_bytes", "lnw_qnet_grad", "lnw_qnet_adam",
+    "lnw_ppolearn_workspace_bytes", "lnw_ppo_grad", "lnw_ppo_clip_adam",
 ]
 
 # lnw_step_kernel codes (include/lnw.h LNW_KERNEL_*)
@@ -114,6 +115,19 @@ class QlearnArgs(C.Structure):  # include/lnw.h: lnw_qlearn_args
                 ("stats_out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+class PpolearnArgs(C.Structure):  # include/lnw.h: lnw_ppolearn_args
+    _fields_ = [("obs", C.c_void_p), ("row_index", C.c_void_p), ("rows", C.c_int64),
+                ("n", C.c_int32), ("D", C.c_int32), ("actions", C.c_void_p),
+                ("old_log_probs", C.c_void_p), ("rtg", C.c_void_p), ("old_values", C.c_void_p),
+                ("eps_clip", C.c_float), ("entropy_coef", C.c_float), ("gamma", C.c_float),
+                ("lambda_", C.c_float), ("freeze_running", C.c_int32),
+                ("actor_params", C.c_void_p), ("critic_params", C.c_void_p),
+                ("actor_grad", C.c_void_p), ("critic_grad", C.c_void_p),
+                ("actor_loss", C.c_void_p), ("critic_loss", C.c_void_p),
+                ("new_log_probs", C.c_void_p), ("entropies", C.c_void_p), ("values", C.c_void_p),
+                ("advantage", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 class LnwError(RuntimeError):
     pass
 
@@ -171,6 +185,10 @@ def load(path=None):
         "lnw_qnet_grad": ([C.POINTER(QlearnArgs), P], C.c_int),
         "lnw_qnet_adam": ([P, P, P, P, I64, P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, P],
                           C.c_int),
+        "lnw_ppolearn_workspace_bytes": ([I64, I32, I32], C.c_int64),
+        "lnw_ppo_grad": ([C.POINTER(PpolearnArgs), P], C.c_int),
+        "lnw_ppo_clip_adam": ([P, P, P, P, I64, P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, P, P],
+                              C.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)

@@ -1,0 +1,406 @@
+"""The learner half of the MAPPO loop: one minibatch update of the reference's
+PPO.learn (ppo.py:321-390) for the blue side, on flat device vectors.
+
+Reference: ppo.py:673-693 (evaluate), ppo.py:695-714 (gae, over the minibatch
+rows as the sequence), ppo.py:716-729 (popart_normalize), ppo.py:342-362 (the
+two losses), ppo.py:371-380 (clip_grad_norm_ and Adam per network),
+ppo.py:311-319 (the prioritised sampler). The kernels are csrc/lnw_ppolearn.hip
+(lnw_ppo_grad, lnw_ppo_clip_adam). learn()'s outer schedule (noise ratio, lr
+halving on victories, epoch count), parameter noise and red-side training stay
+with the caller.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+from torch.distributions import Normal
+
+from .rollout import WINDOW
+
+CONV_PARAMS = 578
+ACTOR_NAMES = ("conv1.weight", "conv1.bias", "norm1.weight", "norm1.bias", "norm1.running_mean",
+               "norm1.running_var", "conv2.weight", "conv2.bias", "norm2.weight", "norm2.bias",
+               "norm2.running_mean", "norm2.running_var", "convhead.weight", "convhead.bias",
+               "layernorm.weight", "layernorm.bias", "fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias",
+               "fc3.weight", "fc3.bias", "normal_head.weight", "log_std_head.weight", "logstd")
+CRITIC_NAMES = ("fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias", "fc3.weight", "fc3.bias", "fc4.weight",
+                "fc4.bias")
+RUNNING = ("norm1.running_mean", "norm1.running_var", "norm2.running_mean", "norm2.running_var")
+
+
+def _slices(names, shapes):
+    out, k = {}, 0
+    for name, shp in zip(names, shapes):
+        out[name] = (k, tuple(shp))
+        k += int(np.prod(shp))
+    return out
+
+
+def actor_slices(n_in):
+    """{state_dict name: (offset, shape)} of the actor's flat layout
+    (include/lnw.h): BatchedActor.packed_features()'s order, then fc1 / fc2 / fc3
+    weight and bias, normal_head, log_std_head and a slot for logstd."""
+    return _slices(ACTOR_NAMES, ((5, 1, 3, 3), (5,), (5,), (5,), (5,), (5,), (8, 5, 3, 3), (8,), (8,), (8,), (8,),
+                                 (8,), (12, 8), (12,), (n_in,), (n_in,), (64, n_in), (64,), (64, 64), (64,),
+                                 (32, 64), (32,), (4, 32), (4, 32), ()))
+
+
+def critic_slices(n, D):
+    """{state_dict name: (offset, shape)} of the critic's flat layout: the
+    state_dict order."""
+    return _slices(CRITIC_NAMES, ((32, n * D), (32,), (64, 32), (64,), (64, 64), (64,), (1, 64), (1,)))
+
+
+def flat_size(sl):
+    return max(k + int(np.prod(s)) for k, s in sl.values())
+
+
+def pack(module, sl):
+    """The module's parameters and running statistics as a flat float32 vector."""
+    sd = module.state_dict()
+    return torch.cat([sd[name].detach().reshape(-1).float() for name in sl]).contiguous()
+
+
+def actor_forward(theta, obs, actions, sl):
+    """MLP.get_dist (network.py:117-152) of every row with the row's own
+    BatchNorm statistics, from a flat parameter vector (differentiable in
+    theta): log-probabilities [B, 4], entropies [B, 4], and the rows'
+    statistics [B, 26] (13 channel means, then their unbiased variances)."""
+    def seg(name):
+        k, shp = sl[name]
+        return theta[k:k + int(np.prod(shp))].reshape(shp)
+
+    B = obs.shape[0]
+    z = obs[:, :WINDOW].reshape(B, 1, 7, 7)
+    z1 = F.conv2d(z, seg("conv1.weight"), seg("conv1.bias"), padding=1)
+    z = F.max_pool2d(F.relu(F.instance_norm(z1, weight=seg("norm1.weight"), bias=seg("norm1.bias"), eps=1e-5)), 2, 2)
+    z2 = F.conv2d(z, seg("conv2.weight"), seg("conv2.bias"), padding=1)
+    z = F.max_pool2d(F.relu(F.instance_norm(z2, weight=seg("norm2.weight"), bias=seg("norm2.bias"), eps=1e-5)), 2, 2)
+    with torch.no_grad():
+        stats = torch.cat([z1.mean((2, 3)), z2.mean((2, 3)), z1.var((2, 3), unbiased=True),
+                           z2.var((2, 3), unbiased=True)], 1)
+    x = torch.cat((F.linear(torch.flatten(z, 1), seg("convhead.weight"), seg("convhead.bias")), obs[:, WINDOW:]), 1)
+    x = F.layer_norm(x, (x.shape[1],), seg("layernorm.weight"), seg("layernorm.bias"), 1e-5)
+    x = torch.tanh(F.linear(x, seg("fc1.weight"), seg("fc1.bias")))
+    x = torch.tanh(F.linear(x, seg("fc2.weight"), seg("fc2.bias")))
+    x = torch.tanh(F.linear(x, seg("fc3.weight"), seg("fc3.bias")))
+    dist = Normal(torch.tanh(F.linear(x, seg("normal_head.weight"))),
+                  torch.exp(F.linear(x, seg("log_std_head.weight"))), validate_args=False)
+    return dist.log_prob(actions), dist.entropy(), stats
+
+
+def critic_forward(theta, gs, sl):
+    """Value.forward (network.py:168-175) from a flat parameter vector: [B]."""
+    def seg(name):
+        k, shp = sl[name]
+        return theta[k:k + int(np.prod(shp))].reshape(shp)
+
+    x = torch.tanh(F.linear(gs, seg("fc1.weight"), seg("fc1.bias")))
+    x = torch.tanh(F.linear(x, seg("fc2.weight"), seg("fc2.bias")))
+    x = torch.tanh(F.linear(x, seg("fc3.weight"), seg("fc3.bias")))
+    return F.linear(x, seg("fc4.weight"), seg("fc4.bias"))[:, 0]
+
+
+def gae_rows(rtg, values, gamma, lambda_, block=512):
+    """PPO.gae (ppo.py:695-714) over the rows of a minibatch as the sequence,
+    returns = gae + values: g_i = delta_i + gamma lambda g_{i+1}, delta_i = rtg_i
+    + gamma v_{i+1} - v_i (no v term after the last row). The recurrence runs in
+    blocks (a triangular matrix of powers per block, a carry between blocks), in
+    the dtype of rtg."""
+    B = rtg.shape[0]
+    nxt = torch.cat([values[1:], torch.zeros_like(values[:1])])
+    delta = rtg + gamma * nxt - values
+    c = gamma * lambda_
+    k = torch.arange(block, device=rtg.device, dtype=rtg.dtype)
+    e = k[None, :] - k[:, None]
+    tri = torch.where(e >= 0, torch.pow(torch.as_tensor(c, dtype=rtg.dtype, device=rtg.device), e.clamp(min=0)),
+                      torch.zeros((), dtype=rtg.dtype, device=rtg.device))
+    g = torch.empty_like(delta)
+    carry = torch.zeros((), dtype=rtg.dtype, device=rtg.device)
+    for hi in range(B, 0, -block):
+        lo = max(hi - block, 0)
+        m = hi - lo
+        # g[lo + i] = sum_{j >= i} c^(j - i) delta[lo + j] + c^(m - i) carry
+        g[lo:hi] = tri[:m, :m] @ delta[lo:hi] + torch.pow(torch.as_tensor(c, dtype=rtg.dtype, device=rtg.device),
+                                                           m - k[:m]) * carry
+        carry = g[lo]
+    return g + values
+
+
+def popart(adv, rtg):
+    """ppo.py:716-729 `popart_normalize` (unbiased std; NaN where it is 0)."""
+    return (adv - adv.mean()) / adv.std() * rtg.std() + rtg.mean()
+
+
+def losses(lp, ent, v, adv, old_lp, rtg, old_v, eps_clip, entropy_coef):
+    """ppo.py:342-362: (actor_loss, critic_loss)."""
+    ratio = torch.exp(lp - old_lp)
+    a = adv[:, None]
+    surr1 = a * ratio
+    surr2 = torch.clamp(ratio, 1 - eps_clip, 1 + eps_clip) * a
+    actor_loss = -(torch.min(surr1, surr2).mean() + entropy_coef * ent.mean())
+    critic_loss = torch.sqrt(torch.max((v - rtg) ** 2,
+                                       (torch.clamp(v, old_v - eps_clip, old_v + eps_clip) - rtg) ** 2).mean())
+    return actor_loss, critic_loss
+
+
+def running_after(r0, stats, momentum=0.1):
+    """The running statistics after one BatchNorm update per row of stats
+    [B, C], rows in order: (1 - m)^B r0 + m sum_i (1 - m)^(B - 1 - i) stat_i, in
+    float64."""
+    B = stats.shape[0]
+    wgt = torch.pow(torch.as_tensor(1.0 - momentum, dtype=torch.float64, device=stats.device),
+                    torch.arange(B - 1, -1, -1, device=stats.device, dtype=torch.float64))
+    return (1.0 - momentum) ** B * r0.double() + momentum * (wgt[:, None] * stats.double()).sum(0)
+
+
+class PPOLearner:
+    """PPO.learn's minibatch update (ppo.py:321-390) for the blue side on flat
+    device vectors: `theta_actor` (actor_slices layout) and `theta_critic`
+    (critic_slices layout), each with Adam moments `m`, `v` and a device step
+    counter.
+
+    One update on B rows, each one (rollout, step, ship), in the order given (the
+    order matters: the reference's gae scans the minibatch rows, and the actor's
+    running statistics take one update per row): the actor row by row with the
+    row's own BatchNorm statistics (BatchedActor's bn="sample"), the critic on
+    the rows' global states, advantage = popart(gae(rtg, V) , rtg), the clipped
+    surrogate with the entropy bonus, the clipped RMSE value loss, and per
+    network clip_grad_norm_(max_grad_norm) and Adam.
+
+    impl="hip": lnw_ppo_grad + lnw_ppo_clip_adam (csrc/lnw_ppolearn.hip), a chain
+    of launches on the current stream with no host synchronisation; capturable
+    in a torch.cuda.graph. impl="torch": the same step with torch ops, autograd,
+    clip_grad_norm_ and torch.optim.Adam on the same flat state, on the host or
+    the device — the arm the kernels are tested and timed against.
+
+    batch (what rows() returns): dict(obs [groups, n, D] float32, index [B] int64
+    rows of obs.reshape(-1, D) or None for all rows in order, actions [B, 4],
+    old_log_probs [B, 4], rtg [B], old_values [B])."""
+
+    def __init__(self, actor, critic, lr=1e-4, eps_clip=0.2, entropy_coef=0.2, gamma=0.99, lambda_=0.95,
+                 max_grad_norm=1.0, betas=(0.9, 0.999), eps=1e-8, impl="hip", device=None):
+        if impl not in ("hip", "torch"):
+            raise ValueError("impl must be 'hip' or 'torch'")
+        if device is None:
+            device = "cuda" if impl == "hip" else next(actor.parameters()).device
+        self.device = dev = torch.device(device)
+        if impl == "hip" and dev.type != "cuda":
+            raise ValueError("impl='hip' needs a GPU device")
+        self.actor, self.critic, self.impl = actor, critic, impl
+        self.lr, self.eps_clip, self.entropy_coef = float(lr), float(eps_clip), float(entropy_coef)
+        self.gamma, self.lambda_, self.max_grad_norm = float(gamma), float(lambda_), float(max_grad_norm)
+        self.betas, self.eps = tuple(betas), float(eps)
+        self.n_in = actor.layernorm.normalized_shape[0]
+        self.D = self.n_in - 12 + WINDOW
+        k1 = critic.fc1.weight.shape[1]
+        if k1 % self.D:
+            raise ValueError("the critic's input is not a whole number of actor observation rows")
+        self.n = k1 // self.D
+        self.actor_sl, self.critic_sl = actor_slices(self.n_in), critic_slices(self.n, self.D)
+        self.theta_actor = pack(actor, self.actor_sl).to(dev)
+        self.theta_critic = pack(critic, self.critic_sl).to(dev)
+        z = torch.zeros_like
+        self.m_actor, self.v_actor = z(self.theta_actor), z(self.theta_actor)
+        self.m_critic, self.v_critic = z(self.theta_critic), z(self.theta_critic)
+        self.step_actor = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.step_critic = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.nbt = torch.tensor([int(actor.norm1.num_batches_tracked)], dtype=torch.int64, device=dev)
+        self._grad_actor, self._grad_critic = z(self.theta_actor), z(self.theta_critic)
+        self._loss = torch.zeros(2, dtype=torch.float32, device=dev)
+        # [actor, critic][clip factor, gradient norm] of the last step()
+        self.clip = torch.zeros((2, 2), dtype=torch.float32, device=dev)
+        self._ws = None
+        self._opt = None
+
+    # ---- batches -------------------------------------------------------------------
+    def rows(self, out, index=None, rtg=None):
+        """A Rollout.run() result as the learner's batch, without copying `obs`:
+        row r = (env, step, ship) of obs.reshape(-1, D); index: the rows of the
+        minibatch in order (None: every row). rtg: a reward-to-go [E, T, n]
+        instead of out["rtg"]; old values are out["values"] repeated per ship."""
+        dev = self.device
+        obs = out["obs"]
+        n, D = obs.shape[-2], obs.shape[-1]
+        obs = obs.reshape(-1, n, D).to(dev, torch.float32).contiguous()
+        rtg = (out["rtg"] if rtg is None else rtg).reshape(-1).to(dev, torch.float32)
+        acts = out["actions"].reshape(-1, 4).to(dev, torch.float32)
+        lps = out["log_probs"].reshape(-1, 4).to(dev, torch.float32)
+        vals = out["values"].reshape(-1).to(dev, torch.float32)
+        if index is None:
+            old_v = vals[:, None].expand(vals.shape[0], n).reshape(-1)
+            return dict(obs=obs, index=None, actions=acts.contiguous(), old_log_probs=lps.contiguous(),
+                        rtg=rtg.contiguous(), old_values=old_v.contiguous())
+        index = index.to(dev, torch.int64).contiguous()
+        return dict(obs=obs, index=index, actions=acts[index].contiguous(), old_log_probs=lps[index].contiguous(),
+                    rtg=rtg[index].contiguous(), old_values=vals[torch.div(index, n, rounding_mode="floor")].contiguous())
+
+    def sample(self, out, batch, generator=None, rtg=None):
+        """ppo.py:311-319: `batch` distinct rows drawn with priorities |rtg| +
+        1e-5 (torch.multinomial without replacement, on the learner's device);
+        the row index [batch] int64 in draw order, for rows()."""
+        rtg = (out["rtg"] if rtg is None else rtg).reshape(-1).to(self.device, torch.float32)
+        pr = torch.abs(rtg) + 1e-5
+        return torch.multinomial(pr / pr.sum(), int(batch), replacement=False, generator=generator)
+
+    def _batch(self, b):
+        dev = self.device
+        f = lambda t: t.to(dev, torch.float32).contiguous()  # noqa: E731
+        obs = f(b["obs"])
+        if obs.dim() != 3 or obs.shape[1] != self.n or obs.shape[2] != self.D:
+            raise ValueError(f"obs must be [groups, {self.n}, {self.D}]")
+        idx = b.get("index")
+        if idx is not None:
+            idx = idx.to(dev, torch.int64).contiguous()
+        return dict(obs=obs, index=idx, actions=f(b["actions"]).reshape(-1, 4),
+                    old_log_probs=f(b["old_log_probs"]).reshape(-1, 4), rtg=f(b["rtg"]).reshape(-1),
+                    old_values=f(b["old_values"]).reshape(-1))
+
+    # ---- HIP arm ---------------------------------------------------------------------
+    def _grad_hip(self, b, want, freeze):
+        from . import _abi
+        L = _abi.load()
+        dev = self.device
+        B = b["rtg"].shape[0]
+        need = L.lnw_ppolearn_workspace_bytes(B, self.n, self.D)
+        if need <= 0:
+            raise _abi.LnwError(f"lnw_ppo_grad does not support rows={B}, n={self.n}, D={self.D}")
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        a = _abi.PpolearnArgs()
+        a.obs, a.rows, a.n, a.D = b["obs"].data_ptr(), B, self.n, self.D
+        a.row_index = b["index"].data_ptr() if b["index"] is not None else None
+        a.actions, a.old_log_probs = b["actions"].data_ptr(), b["old_log_probs"].data_ptr()
+        a.rtg, a.old_values = b["rtg"].data_ptr(), b["old_values"].data_ptr()
+        a.eps_clip, a.entropy_coef, a.gamma, a.lambda_ = self.eps_clip, self.entropy_coef, self.gamma, self.lambda_
+        a.freeze_running = int(freeze)
+        a.actor_params, a.critic_params = self.theta_actor.data_ptr(), self.theta_critic.data_ptr()
+        a.actor_grad, a.critic_grad = self._grad_actor.data_ptr(), self._grad_critic.data_ptr()
+        a.actor_loss, a.critic_loss = self._loss.data_ptr(), self._loss.data_ptr() + 4
+        out = {}
+        if want:
+            out["new_log_probs"] = torch.empty((B, 4), dtype=torch.float32, device=dev)
+            out["entropies"] = torch.empty((B, 4), dtype=torch.float32, device=dev)
+            out["values"] = torch.empty(B, dtype=torch.float32, device=dev)
+            out["advantage"] = torch.empty(B, dtype=torch.float32, device=dev)
+            a.new_log_probs, a.entropies = out["new_log_probs"].data_ptr(), out["entropies"].data_ptr()
+            a.values, a.advantage = out["values"].data_ptr(), out["advantage"].data_ptr()
+        a.workspace, a.workspace_bytes = self._ws.data_ptr(), self._ws.numel()
+        _abi.check(L.lnw_ppo_grad(C.byref(a), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        return out
+
+    def _adam_hip(self):
+        from . import _abi
+        L = _abi.load()
+        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        for k, (th, g, m, v, cnt) in enumerate(((self.theta_actor, self._grad_actor, self.m_actor, self.v_actor,
+                                                 self.step_actor),
+                                                (self.theta_critic, self._grad_critic, self.m_critic, self.v_critic,
+                                                 self.step_critic))):
+            _abi.check(L.lnw_ppo_clip_adam(th.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), th.numel(),
+                                           cnt.data_ptr(), self.lr, self.betas[0], self.betas[1], self.eps,
+                                           self.max_grad_norm, self.clip.data_ptr() + 8 * k, st))
+
+    # ---- torch arm -------------------------------------------------------------------
+    def _grad_torch(self, b, freeze):
+        n, D = self.n, self.D
+        flat = b["obs"].reshape(-1, D)
+        gs_all = b["obs"].reshape(-1, n * D)
+        if b["index"] is None:
+            obs = flat
+            gs = gs_all.repeat_interleave(n, 0)
+        else:
+            obs = flat[b["index"]]
+            gs = gs_all[torch.div(b["index"], n, rounding_mode="floor")]
+        tha = self.theta_actor.detach().clone().requires_grad_(True)
+        thc = self.theta_critic.detach().clone().requires_grad_(True)
+        lp, ent, stats = actor_forward(tha, obs, b["actions"], self.actor_sl)
+        v = critic_forward(thc, gs, self.critic_sl)
+        with torch.no_grad():
+            adv = popart(gae_rows(b["rtg"], v.detach(), self.gamma, self.lambda_), b["rtg"])
+        al, cl = losses(lp, ent, v, adv, b["old_log_probs"], b["rtg"], b["old_values"], self.eps_clip,
+                        self.entropy_coef)
+        al.backward()
+        cl.backward()
+        self._grad_actor.copy_(tha.grad)
+        self._grad_critic.copy_(thc.grad)
+        self._loss.copy_(torch.stack([al.detach(), cl.detach()]))
+        if not freeze:
+            with torch.no_grad():
+                for name, lo, hi in (("norm1.running_mean", 0, 5), ("norm2.running_mean", 5, 13),
+                                     ("norm1.running_var", 13, 18), ("norm2.running_var", 18, 26)):
+                    k, shp = self.actor_sl[name]
+                    seg = self.theta_actor[k:k + shp[0]]
+                    seg.copy_(running_after(seg, stats[:, lo:hi]).float())
+        return dict(new_log_probs=lp.detach(), entropies=ent.detach(), values=v.detach(), advantage=adv)
+
+    def _adam_torch(self):
+        if self._opt is None:
+            self._p, self._opt = [], []
+            for th, m, v in ((self.theta_actor, self.m_actor, self.v_actor),
+                             (self.theta_critic, self.m_critic, self.v_critic)):
+                p = nn.Parameter(th)  # (shares the vector's storage)
+                opt = torch.optim.Adam([p], lr=self.lr, betas=self.betas, eps=self.eps)
+                st = opt.state[p]
+                st["step"], st["exp_avg"], st["exp_avg_sq"] = torch.tensor(0.0), m, v
+                self._p.append(p)
+                self._opt.append(opt)
+        for k, (g, cnt) in enumerate(((self._grad_actor, self.step_actor), (self._grad_critic, self.step_critic))):
+            self._p[k].grad = g.clone()
+            norm = torch.nn.utils.clip_grad_norm_([self._p[k]], self.max_grad_norm)
+            self.clip[k, 0] = torch.clamp(self.max_grad_norm / (norm + 1e-6), max=1.0)
+            self.clip[k, 1] = norm
+            self._opt[k].step()
+            cnt += 1
+
+    # ---- public ------------------------------------------------------------------------
+    def grad(self, batch, update_running=True):
+        """Losses and gradients of one minibatch, without the optimiser step:
+        dict(actor_loss, critic_loss 0-d; actor_grad, critic_grad unclipped, in
+        the flat layouts; actor_norm, critic_norm their L2 norms;
+        new_log_probs [B, 4], entropies [B, 4], values [B], advantage [B]). The
+        actor's running statistics and batch counter take the B updates of the
+        reference's evaluate() unless update_running is False."""
+        b = self._batch(batch)
+        if self.impl == "hip":
+            out = self._grad_hip(b, True, not update_running)
+        else:
+            out = self._grad_torch(b, not update_running)
+        if update_running:
+            self.nbt += b["rtg"].shape[0]
+        out["actor_loss"], out["critic_loss"] = self._loss[0].clone(), self._loss[1].clone()
+        out["actor_grad"], out["critic_grad"] = self._grad_actor.clone(), self._grad_critic.clone()
+        out["actor_norm"] = torch.linalg.vector_norm(out["actor_grad"])
+        out["critic_norm"] = torch.linalg.vector_norm(out["critic_grad"])
+        return out
+
+    def step(self, batch):
+        """One minibatch update: gradients, clip_grad_norm_, Adam, for the actor
+        and the critic. Returns (actor_loss, critic_loss), 0-d device tensors
+        (nothing synchronises with the host)."""
+        b = self._batch(batch)
+        if self.impl == "hip":
+            self._grad_hip(b, False, False)
+            self._adam_hip()
+        else:
+            self._grad_torch(b, False)
+            self._adam_torch()
+        self.nbt += b["rtg"].shape[0]
+        return self._loss[0].clone(), self._loss[1].clone()
+
+    @torch.no_grad()
+    def export(self):
+        """Write both vectors, the running statistics and num_batches_tracked
+        back into the BatchedActor / BatchedCritic modules, on the device they
+        live on (device-to-device copies: no host round trip); returns (actor,
+        critic). The next Rollout.run() acts with the updated weights."""
+        for net, theta, sl in ((self.actor, self.theta_actor, self.actor_sl),
+                               (self.critic, self.theta_critic, self.critic_sl)):
+            sd = net.state_dict()  # (tensors sharing the module's storage)
+            for name, (k, shp) in sl.items():
+                sd[name].copy_(theta[k:k + int(np.prod(shp))].reshape(shp))
+        for nm in (self.actor.norm1, self.actor.norm2):
+            nm.num_batches_tracked.copy_(self.nbt[0])
+        return self.actor, self.critic
