@@ -403,6 +403,83 @@ typedef struct lnw_policy_args {
 } lnw_policy_args;
 int lnw_policy_act(const lnw_policy_args *args, void *stream);
 
+/* ---- parameter-noise exploration: a population of actors in one rollout ------
+ * The reference explores by parameter noise (ppo.py:452-482, 669): every rollout
+ * episode reloads the noiseless actor and adds clamp(N(0, noise_ratio), -clip,
+ * +clip) to each actor parameter whose name holds none of norm1, norm2,
+ * layernorm; the episode's actions and old log-probabilities come from that
+ * actor. Here the envs of a rollout are split into members of G consecutive
+ * global envs (member m = global envs [m G, (m + 1) G); G = 1 is the reference:
+ * one noised actor per episode), lnw_actor_perturb writes every member's packed
+ * parameter set once per rollout, and lnw_policy_act_pop acts for each env with
+ * its member's set.
+ *
+ * Flat actor vector (P = lnw_ppolearn_args' actor layout, P = 7139 + 66 n_in
+ * floats, n_in = D - 37): the conv head / LayerNorm block in
+ * BatchedActor.packed_features()'s order, then fc1 w [64][n_in], b; fc2 w, b;
+ * fc3 w, b; normal_head w [4][32]; log_std_head w [4][32]; logstd.
+ * Packed set (lnw_policy_packed_floats(D) floats, what lnw_policy_act reads and
+ * BatchedActor.packed_policy() produces): that block zero-padded to a multiple
+ * of 4 floats; b1 [64], b2 [64], b3 [32]; then per layer (fc1 with n_in zero-
+ * padded to 32 columns, 64 when n_in > 32; fc2; fc3; the heads: normal rows
+ * 0-3, log-std rows 4-7, zero rows to 16) three planes hi, mid, lo of bfloat16
+ * x 8 [n-tile][k-pair p][lane], element j = W[16 nt + lane % 16][32 p + 16 (j /
+ * 4) + 4 (lane / 16) + j % 4], w = hi + mid + lo exactly (each term rounded to
+ * nearest).
+ *
+ * Member m's parameters: theta_m = theta + mask * clamp(sigma * z_m, -clip,
+ * +clip), in float32 in that order (ppo.py:474-475).
+ *   mask: 1 on conv1, conv2, convhead, fc1, fc2, fc3 weights and biases and on
+ *     the two head weights; 0 on norm1.*, norm2.* (running statistics included),
+ *     layernorm.* and the logstd slot (the reference noises logstd too; nothing
+ *     ever reads it, and the packed set does not hold it).
+ *   z_m[k], k < P: the keyed standard normal of flat index k (masked ones are
+ *     drawn and discarded), keyed_normal(row0 = m, rows = 1, cols = P, seed, slot)
+ *     of lnw/rollout.py: the uniforms lnw_fill_uniform_f32(seed) holds at
+ *     (slot << 40) + 2 P m + k and + P + k, through Box-Muller.
+ *   slot = (call * T) * 4 + 3, call read from call_dev (NULL = 0): a rollout's
+ *     action draws use slots (call * T + t) * 4 + which with which 0 (blue
+ *     sample), 1 (blue action noise) and 2 (red sample) only, so which = 3 of
+ *     step 0 is free. (member0 + members) * 2 P must stay below 2^40.
+ *   sigma = noise_dev[0], clip = noise_dev[1], read on the device, so a captured
+ *     graph follows in-place updates of the schedule. noise_dev == NULL or sigma
+ *     == 0: theta_m = theta bit for bit (an exact repack, no draws).
+ * theta_member_stride != 0: member k (local) reads its own vector at theta + k *
+ * theta_member_stride instead of sharing one. One launch, no atomics, no host
+ * synchronisation, bitwise reproducible; 0 B of scratch. */
+typedef struct lnw_actor_perturb_args {
+  const float *theta;          /* flat actor vector(s), see above */
+  int64_t theta_member_stride; /* floats between the members' vectors (>= P), or 0: one for all */
+  int32_t D;                   /* observation row length (limits as lnw_policy_act) */
+  int32_t T;                   /* rollout steps (the slot); > 0 with noise_dev */
+  int64_t member0, members;    /* global id of the first member written, how many */
+  float *packed_out;           /* member member0 + k at packed_out + k * member_stride (16-B aligned) */
+  int64_t member_stride;       /* floats, >= lnw_policy_packed_floats(D), a multiple of 4 */
+  const float *noise_dev;      /* NULL, or [2] = sigma, clip on the device */
+  uint64_t seed;
+  const int64_t *call_dev;     /* rollout index, read on the device (NULL = 0) */
+} lnw_actor_perturb_args;
+int64_t lnw_policy_packed_floats(int32_t D); /* 0 for unsupported D */
+int lnw_actor_perturb(const lnw_actor_perturb_args *args, void *stream);
+
+/* lnw_policy_act for a population: the E local envs in members of
+ * envs_per_member consecutive envs (the last may hold fewer), member k acting
+ * with the packed set at args->params + k * member_stride (args->params: the
+ * set of the member that owns local env 0; 16-B aligned). A workgroup serves
+ * rows of one member: grid = members x ceil(envs_per_member n / 512), most
+ * efficient where envs_per_member n is a multiple of 512. Everything else — the
+ * keyed sample by global row, forced actions, scripted rows, kinds, rollout
+ * rows, live / alive — is lnw_policy_act's, bit for bit what lnw_policy_act
+ * computes for the member's envs alone with the member's set.
+ * By design: a row whose heads are NaN takes lnw_policy_act's guard (mean 0, std
+ * 1); the reference reloads the noiseless actor for the rest of the episode
+ * (ppo.py:505-507). */
+typedef struct lnw_policy_pop {
+  int64_t envs_per_member;     /* G > 0 */
+  int64_t member_stride;       /* floats, >= lnw_policy_packed_floats(D), a multiple of 4 */
+} lnw_policy_pop;
+int lnw_policy_act_pop(const lnw_policy_args *args, const lnw_policy_pop *pop, void *stream);
+
 /* After lnw_step: the rollout's bookkeeping of step t (ppo.py:598-641) and the
  * critic (Value, network.py:154-172) on the rows the actor saw: value (0 after
  * the episode ended), rewards (ditto), running flag, and live &= done != 0. */

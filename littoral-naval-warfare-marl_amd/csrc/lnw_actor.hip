@@ -19,6 +19,7 @@
 #include <cmath>
 #include <cstdint>
 #include <string>
+#include <type_traits>
 
 #include "lnw.h"
 #include "lnw_device.h"
@@ -33,6 +34,8 @@ typedef double f64x4 __attribute__((ext_vector_type(4)));
 // the conv head (bn_relu, conv_head_win, conv_head_row, load_tail_q), its packed
 // parameter layout and the supported observation width (MAX_IN, obs_width_ok)
 #include "lnw_convhead.inc"
+// the packed parameter set's layout (FC1 .. NOUT, mlp_bf16x8, policy_pack)
+#include "lnw_policypack.inc"
 
 constexpr float LN_EPS = 1e-5f;
 
@@ -122,8 +125,6 @@ __global__ __launch_bounds__(CH_THREADS, 1) void features_kernel(const float *pa
 // eps = sqrt(-2 log1p(-u_c)) cos(2 pi u_{4+c}); `call` is read from device
 // memory so a replayed graph draws fresh values every rollout.
 // ---------------------------------------------------------------------------
-constexpr int FC1 = 64, FC2 = 64, FC3 = 32, NOUT = 4;
-
 struct PolicyArgs {
   lnw_policy_args a;
   int n_in;
@@ -146,8 +147,7 @@ __device__ __forceinline__ void keyed_eps(unsigned long long seed, unsigned long
   float u[8];
   philox_u8(seed, (slot << 38) + (unsigned long long)grow * 2ull, u);
 #pragma unroll
-  for (int c = 0; c < NOUT; c++)  // (v_cos_f32 takes revolutions: cos(2 pi u) without the range reduction)
-    eps[c] = sqrtf(-2.0f * log1pf(-u[c])) * __builtin_amdgcn_cosf(u[4 + c]);
+  for (int c = 0; c < NOUT; c++) eps[c] = box_muller(u[c], u[4 + c]);
 }
 
 // ---- the MLP on the matrix cores -------------------------------------------
@@ -280,18 +280,11 @@ __device__ __forceinline__ void tanh_all(f32x4v (&acc)[4][NTO]) {
       for (int v = 0; v < 4; v++) acc[rt][nt][v] = tanh_fast(acc[rt][nt][v]);
 }
 
-// bf16x8 elements of the MLP's packed weights (three planes per layer: fc1
-// 4 x Q1/2, fc2 4 x 2, fc3 2 x 2, heads 1 x 1 tiles of WAVE, as mlp_heads reads them)
-template <int NI>
-__host__ __device__ constexpr int mlp_bf16x8() {
-  return 3 * (4 * (NI / 32) + 4 * 2 + 2 * 2 + 1 * 1) * WAVE;
-}
-
 // fc1 / fc2 / fc3 and both heads of the wave's 64 rows on the matrix cores
 // (xb: fc1's B operand), then each row's head outputs brought to its own lane
-template <int Q1>
-__device__ __forceinline__ void mlp_heads(const PolicyArgs &pa, const bf16x8 *Fw, const float *xt, int lane,
-                                          int g, int m, float (&mean)[NOUT], float (&lsd)[NOUT]) {
+template <int Q1, class PF>
+__device__ __forceinline__ void mlp_heads(const PolicyArgs &pa, PF pofs, const bf16x8 *Fw, const float *xt,
+                                          int lane, int g, int m, float (&mean)[NOUT], float (&lsd)[NOUT]) {
   constexpr int KS = 16 * Q1 + 4;  // the tile's row stride (policy_act_kernel)
   const lnw_policy_args &a = pa.a;
   f32x4v xb[4][Q1];
@@ -302,7 +295,8 @@ __device__ __forceinline__ void mlp_heads(const PolicyArgs &pa, const bf16x8 *Fw
   // weights: three bf16 planes per layer (mfma_layer3), layers in order
   // Fw: the three bf16 planes of every layer (global, or the block's LDS copy)
   constexpr int O2 = 3 * 4 * (Q1 / 2) * WAVE, O3 = O2 + 3 * 4 * 2 * WAVE, OH = O3 + 3 * 2 * 2 * WAVE;
-  const float *bias = a.params + pa.off_b1;  // b1 [64] | b2 [64] | b3 [32]
+  // b1 [64] | b2 [64] | b3 [32] of the block's parameter set (pofs() floats into params)
+  const float *bias = a.params + pofs() + pa.off_b1;
   f32x4v h1[4][4];
   bias_init<4>(bias, h1, g);
   mfma_layer3<4, Q1>(Fw, xb, h1, lane);
@@ -340,10 +334,10 @@ __device__ __forceinline__ void mlp_heads(const PolicyArgs &pa, const bf16x8 *Fw
 // A wave's rows up to the fc1 tile: conv head + LayerNorm (one row per lane),
 // the observation copy for the rollout buffer, and the LayerNorm outputs into
 // the wave's fc1 input tile in LDS (xt) for mlp_heads.
-template <int NI>
+// (R: the type of row indices, long long, or int in the population kernel)
+template <int NI, class R>
 __device__ __forceinline__ void head_to_tile(const PolicyArgs &pa, const float *P, float *warea, int lane,
-                                             bool valid, long long e, int i, long long istride, long long r0,
-                                             long long rows) {
+                                             bool valid, long long e, int i, long long istride, R r0, R rows) {
   constexpr int KS = NI + 4;
   const lnw_policy_args &a = pa.a;
   const int n = a.n, D = a.D, n_in = pa.n_in;
@@ -386,17 +380,18 @@ __device__ __forceinline__ void head_to_tile(const PolicyArgs &pa, const float *
   const bool in_place = a.obs_out == a.obs && a.obs_env_stride == istride;
   if (a.obs_out && (!in_place || a.live)) {
     const int D4 = D >> 2;
-    const long long rw = r0 + (threadIdx.x & ~(WAVE - 1));
-    const long long nr = rows - rw < WAVE ? rows - rw : WAVE;
+    const R rw = r0 + (threadIdx.x & ~(WAVE - 1));
+    const R nr = rows - rw < WAVE ? rows - rw : WAVE;
     for (int q = lane; q < nr * D4; q += WAVE) {
-      const long long rr = rw + q / D4;
+      const R rr = rw + q / D4;
       const int c4 = q - (q / D4) * D4;
-      const long long ee = rr / n;
+      const R ee = rr / n;
       const int ii = (int)(rr - ee * n);
       const bool dead = a.live && !a.live[ee];
       if (in_place && !dead) continue;
-      f32x4 v = dead ? f32x4{0.f, 0.f, 0.f, 0.f} : *(const f32x4 *)(a.obs + ee * istride + (long long)ii * D + 4 * c4);
-      *(f32x4 *)(a.obs_out + ee * a.obs_env_stride + (long long)ii * D + 4 * c4) = v;
+      f32x4 v = dead ? f32x4{0.f, 0.f, 0.f, 0.f}
+                     : *(const f32x4 *)(a.obs + (long long)ee * istride + (long long)ii * D + 4 * c4);
+      *(f32x4 *)(a.obs_out + (long long)ee * a.obs_env_stride + (long long)ii * D + 4 * c4) = v;
     }
   }
   // ---- fc1 input tile: the wave's rows into the MFMA B layout ---------------
@@ -417,18 +412,33 @@ __device__ __forceinline__ void head_to_tile(const PolicyArgs &pa, const float *
 // heads beside heads and MLPs beside MLPs are exact. (One block per CU: the
 // block's LDS is larger than half the CU's, so no other block's head shares a
 // SIMD with these MLPs.)
-template <int NI>
-__device__ __forceinline__ void head_and_mlp(const PolicyArgs &pa, const float *P, const bf16x8 *Fw, float *warea, int lane, int g,
-                                             int m, bool valid, long long e, int i, long long istride, long long r0,
-                                             long long rows, float (&mean)[NOUT], float (&lsd)[NOUT]) {
+template <int NI, class PF, class R>
+__device__ __forceinline__ void head_and_mlp(const PolicyArgs &pa, const float *P, PF pofs, const bf16x8 *Fw,
+                                             float *warea, int lane, int g, int m, bool valid, long long e, int i,
+                                             long long istride, R r0, R rows, float (&mean)[NOUT],
+                                             float (&lsd)[NOUT]) {
   constexpr int Q1 = NI / 16;
   head_to_tile<NI>(pa, P, warea, lane, valid, e, i, istride, r0, rows);
   __syncthreads();  // every head done before any MLP
-  mlp_heads<Q1>(pa, Fw, warea, lane, g, m, mean, lsd);
+  mlp_heads<Q1>(pa, pofs, Fw, warea, lane, g, m, mean, lsd);
 }
 
-template <int NI>
-__global__ __launch_bounds__(PA_THREADS, 1) void policy_act_kernel(PolicyArgs pa) {
+// Population launch (lnw_policy_act_pop): the local envs in members of G
+// consecutive envs, member k acting with the packed set at params + k *
+// member_stride. A workgroup serves rows of one member only: block b of member
+// k (blockIdx.x = k * bpm + b) takes the member's rows [512 b, 512 b + 512) of
+// its G n (fewer in the last member).
+struct PolicyPopArgs : PolicyArgs {
+  int member_rows;    // G n
+  int member_stride;  // floats between the members' packed sets
+  int bpm;            // blocks per member
+};
+
+template <bool POP>
+using PolicyKernelArgs = std::conditional_t<POP, PolicyPopArgs, PolicyArgs>;
+
+template <int NI, bool POP>
+__global__ __launch_bounds__(PA_THREADS, 1) void policy_act_kernel(PolicyKernelArgs<POP> pa) {
   constexpr int KS = NI + 4;         // row stride of the wave's fc1 input tile (16-B aligned)
   const lnw_policy_args &a = pa.a;
   const int n_in = pa.n_in;
@@ -438,25 +448,55 @@ __global__ __launch_bounds__(PA_THREADS, 1) void policy_act_kernel(PolicyArgs pa
   // wave's fc1 input tile [64][KS] over the same floats
   constexpr int WAREA = (45 > KS ? 45 : KS) * WAVE;
   float *warea = actor_lds + ((n_par + 3) & ~3) + (threadIdx.x / WAVE) * WAREA;
-  for (int i = threadIdx.x; i < n_par; i += blockDim.x) P[i] = a.params[i];
+  // the block's member (POP), from blockIdx at every use through an opaque
+  // copy, so that nothing of it lives across the head, where the registers are
+  // full; and its parameter set within params: the one set (0), or its member's
+  auto member = [&]() {
+    int k = 0;
+    if constexpr (POP) {
+      k = blockIdx.x / pa.bpm;
+      asm volatile("" : "+s"(k));
+    }
+    return k;
+  };
+  auto pofs = [&]() -> long long {
+    if constexpr (POP) return (long long)member() * pa.member_stride;
+    else return 0;
+  };
+  for (int i = threadIdx.x; i < n_par; i += blockDim.x) P[i] = a.params[pofs() + i];
   // the MLP's weights (three bf16 planes per layer, mlp_bf16x8<NI> of them):
   // at NI = 32 a copy in LDS after the wave areas, loaded once per block while
   // the heads run, so each wave's MFMA chains read their A operands from LDS
   // instead of 51 KB apiece from L2 (at NI = 64 they do not fit beside the
   // larger tiles and stay in global memory)
-  const bf16x8 *Fw = (const bf16x8 *)(a.params + pa.off_w1);
+  const bf16x8 *Fw = (const bf16x8 *)(a.params + pofs() + pa.off_w1);
   if constexpr (NI == 32) {
     bf16x8 *wl = (bf16x8 *)(actor_lds + ((n_par + 3) & ~3) + (PA_THREADS / WAVE) * WAREA);
     for (int i = threadIdx.x; i < mlp_bf16x8<NI>(); i += blockDim.x) wl[i] = Fw[i];
     Fw = wl;
   }
   const int n = a.n, D = a.D;
-  const long long rows = a.E * n;
-  const long long r0 = (long long)blockIdx.x * PA_THREADS;
+  // the block's first row and the end of its rows: every row in order, or (POP)
+  // the rows of its member, there as 32-bit values (rows + PA_THREADS < 2^31,
+  // checked on the host): with 64-bit ones the 64-wide kernel spilled 8 B more
+  using R = std::conditional_t<POP, int, long long>;
+  auto block_rows = [&](R &first, R &end) {
+    if constexpr (POP) {
+      const int k = member();
+      const long long all = a.E * n, mend = (long long)(k + 1) * pa.member_rows;
+      end = (int)(mend < all ? mend : all);
+      first = k * pa.member_rows + (int)(blockIdx.x - k * pa.bpm) * PA_THREADS;
+    } else {
+      end = a.E * n;
+      first = (long long)blockIdx.x * PA_THREADS;
+    }
+  };
+  R r0, rows;
+  block_rows(r0, rows);
   const long long istride = a.obs_in_env_stride ? a.obs_in_env_stride : (long long)n * D;
   __syncthreads();
   const int lane = threadIdx.x & (WAVE - 1), g = lane >> 4, m = lane & 15;
-  const long long r = r0 + threadIdx.x;
+  const R r = r0 + threadIdx.x;
   const bool valid = r < rows;  // (every lane stays for the wave-wide MFMAs)
   // (32-bit: rows < 2^31, checked on the host; fewer registers live across the head)
   const int e32 = valid ? (int)r / n : 0;
@@ -487,12 +527,17 @@ __global__ __launch_bounds__(PA_THREADS, 1) void policy_act_kernel(PolicyArgs pa
   }
   // ---- head, fc1 tile and MLP (phases: head_and_mlp) --------------------------
   float mean[NOUT], lsd[NOUT];
-  head_and_mlp<NI>(pa, P, Fw, warea, lane, g, m, valid, e, i, istride, r0, rows, mean, lsd);
+  head_and_mlp<NI>(pa, P, pofs, Fw, warea, lane, g, m, valid, e, i, istride, r0, rows, mean, lsd);
   if (!valid) return;
   // the row's env and ship again, from an opaque copy of the row index: so
   // they are recomputed here instead of living across the head (where the
   // register file is full and they would go to scratch)
   int r_o = (int)(blockIdx.x * PA_THREADS + threadIdx.x);
+  if constexpr (POP) {  // (from blockIdx again: nothing of it lives across the head)
+    R first, end;
+    block_rows(first, end);
+    r_o = (int)first + (int)threadIdx.x;
+  }
   asm volatile("" : "+v"(r_o));
   const int e_o = r_o / n, i_o = r_o - e_o * n;
   float std_[NOUT];
@@ -741,7 +786,8 @@ int lnw_actor_features(const float *params_dev, int32_t obs_dim, const float *ob
 // 32, or 64 when n_in > 32), fc2, fc3 and the heads (normal rows 0-3, log-std
 // rows 4-7, zero rows to 16), each as float4 [n-tile][k-quad][lane] (see
 // mfma_layer).
-int lnw_policy_act(const lnw_policy_args *args, void *stream) {
+// (pop == NULL: lnw_policy_act's one set for every row)
+static int policy_launch(const lnw_policy_args *args, const lnw_policy_pop *pop, void *stream) {
   if (!args) return LNW_EINVAL;
   const lnw_policy_args &a = *args;
   if (!a.obs || !a.params || !a.alive || a.n <= 0 || a.E < 0 || a.A <= 0 || a.own0 < 0 || a.own0 + a.n > a.A)
@@ -760,18 +806,31 @@ int lnw_policy_act(const lnw_policy_args *args, void *stream) {
       (a.logp_out && ((uintptr_t)a.logp_out & 15)) || (a.full && ((uintptr_t)a.full & 31)) ||
       (a.script && ((uintptr_t)a.script & 31)))
     return LNW_EINVAL;
+  const PolicyPack pk = policy_pack(a.D);
+  if (pop && (pop->envs_per_member <= 0 || pop->member_stride < pk.floats || (pop->member_stride & 3) ||
+              ((uintptr_t)a.params & 15)))
+    return LNW_EINVAL;
   if (a.E == 0) return 0;
-  PolicyArgs pa;
+  PolicyPopArgs pa;  // (the plain kernels take its PolicyArgs part)
   pa.a = a;
-  pa.n_in = a.D - WIN + 12;
-  int o = CONV_PARAMS + 2 * pa.n_in;
-  o = (o + 3) & ~3;     // (16-B aligned biases and fragments)
-  pa.off_b1 = o; o += FC1 + FC2 + FC3;
-  pa.off_w1 = o;
+  pa.n_in = pk.n_in;
+  pa.off_b1 = pk.off_b1;
+  pa.off_w1 = pk.off_w1;
   const long long rows = a.E * a.n;
   if (rows + PA_THREADS >= (1ll << 31)) return LNW_EUNSUPPORTED;  // (32-bit row indices)
-  const unsigned blocks = (unsigned)((rows + PA_THREADS - 1) / PA_THREADS);
-  const int npar4 = (CONV_PARAMS + 2 * pa.n_in + 3) & ~3;
+  long long nblocks = (rows + PA_THREADS - 1) / PA_THREADS;
+  if (pop) {  // members x blocks of one member (the last member may hold fewer envs)
+    const long long G = pop->envs_per_member < a.E ? pop->envs_per_member : a.E;
+    const long long members = (a.E + G - 1) / G;
+    if (pop->member_stride >= (1ll << 31)) return LNW_EUNSUPPORTED;
+    pa.member_rows = (int)(G * a.n);  // (<= rows: 32-bit)
+    pa.member_stride = (int)pop->member_stride;
+    pa.bpm = (pa.member_rows + PA_THREADS - 1) / PA_THREADS;
+    nblocks = members * pa.bpm;
+    if (nblocks >= (1ll << 31)) return LNW_EUNSUPPORTED;
+  }
+  const unsigned blocks = (unsigned)nblocks;
+  const int npar4 = pk.off_b1;
   size_t lds = (size_t)(npar4 + (PA_THREADS / WAVE) * (pa.n_in <= 32 ? 45 : MAX_IN + 4) * WAVE) * sizeof(float);
   if (pa.n_in <= 32) lds += (size_t)mlp_bf16x8<32>() * 16;  // the MLP weights' LDS copy
   // One block per CU: head_and_mlp's schedule (every head, a barrier, every MLP)
@@ -788,11 +847,23 @@ int lnw_policy_act(const lnw_policy_args *args, void *stream) {
     cu_lds = v;
   }
   if (lds <= (size_t)cu_lds / 2) lds = (size_t)cu_lds / 2 + 16;
-  if (pa.n_in <= 32)
-    policy_act_kernel<32><<<blocks, PA_THREADS, lds, (hipStream_t)stream>>>(pa);
+  const PolicyArgs &plain = pa;
+  if (pop && pa.n_in <= 32)
+    policy_act_kernel<32, true><<<blocks, PA_THREADS, lds, (hipStream_t)stream>>>(pa);
+  else if (pop)
+    policy_act_kernel<MAX_IN, true><<<blocks, PA_THREADS, lds, (hipStream_t)stream>>>(pa);
+  else if (pa.n_in <= 32)
+    policy_act_kernel<32, false><<<blocks, PA_THREADS, lds, (hipStream_t)stream>>>(plain);
   else
-    policy_act_kernel<MAX_IN><<<blocks, PA_THREADS, lds, (hipStream_t)stream>>>(pa);
+    policy_act_kernel<MAX_IN, false><<<blocks, PA_THREADS, lds, (hipStream_t)stream>>>(plain);
   return hipGetLastError() == hipSuccess ? 0 : LNW_EDEVICE;
+}
+
+int lnw_policy_act(const lnw_policy_args *args, void *stream) { return policy_launch(args, nullptr, stream); }
+
+int lnw_policy_act_pop(const lnw_policy_args *args, const lnw_policy_pop *pop, void *stream) {
+  if (!pop) return LNW_EINVAL;
+  return policy_launch(args, pop, stream);
 }
 
 // Packed critic: see rollout_post_kernel (BatchedCritic.packed()).

@@ -199,6 +199,14 @@ __device__ inline void philox_u4(unsigned long long seed, unsigned long long ctr
   for (int k = 0; k < 4; k++) u[k] = (float)(o[k] >> 8) * 5.9604644775390625e-08f;
 }
 
+// The standard normal of two such uniforms (keyed_normal in lnw/rollout.py):
+// sqrt(-2 log1p(-ur)) cos(2 pi ua); v_cos_f32 takes revolutions, so cos(2 pi u)
+// needs no range reduction. The policy's action draws and lnw_actor_perturb's
+// parameter noise are both made of these.
+__device__ __forceinline__ float box_muller(float ur, float ua) {
+  return sqrtf(-2.0f * log1pf(-ur)) * __builtin_amdgcn_cosf(ua);
+}
+
 __device__ inline double u53(uint32_t a, uint32_t b) {
   return ((double)(a >> 5) * 67108864.0 + (double)(b >> 6)) / 9007199254740992.0;
 }

@@ -34,6 +34,7 @@ SYMBOLS = [
     "lnw_policy_act", "lnw_rollout_post", "lnw_qnet_act",
     "lnw_qlearn_workspace_bytes", "lnw_qnet_grad", "lnw_qnet_adam",
     "lnw_ppolearn_workspace_bytes", "lnw_ppo_grad", "lnw_ppo_clip_adam",
+    "lnw_policy_packed_floats", "lnw_actor_perturb", "lnw_policy_act_pop",
 ]
 
 # lnw_step_kernel codes (include/lnw.h LNW_KERNEL_*)
@@ -82,6 +83,17 @@ class PolicyArgs(C.Structure):  # include/lnw.h: lnw_policy_args
                 ("script_cnt", C.c_int32), ("kinds", C.c_void_p), ("kinds_f32_all_alive", C.c_int32),
                 ("f32_out", C.c_void_p), ("f32_env_stride", C.c_int64),
                 ("obs_in_env_stride", C.c_int64)]
+
+
+class ActorPerturbArgs(C.Structure):  # include/lnw.h: lnw_actor_perturb_args
+    _fields_ = [("theta", C.c_void_p), ("theta_member_stride", C.c_int64),
+                ("D", C.c_int32), ("T", C.c_int32), ("member0", C.c_int64), ("members", C.c_int64),
+                ("packed_out", C.c_void_p), ("member_stride", C.c_int64),
+                ("noise_dev", C.c_void_p), ("seed", C.c_uint64), ("call_dev", C.c_void_p)]
+
+
+class PolicyPop(C.Structure):  # include/lnw.h: lnw_policy_pop
+    _fields_ = [("envs_per_member", C.c_int64), ("member_stride", C.c_int64)]
 
 
 class RolloutPostArgs(C.Structure):  # include/lnw.h: lnw_rollout_post_args
@@ -189,6 +201,9 @@ def load(path=None):
         "lnw_ppo_grad": ([C.POINTER(PpolearnArgs), P], C.c_int),
         "lnw_ppo_clip_adam": ([P, P, P, P, I64, P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, P, P],
                               C.c_int),
+        "lnw_policy_packed_floats": ([I32], C.c_int64),
+        "lnw_actor_perturb": ([C.POINTER(ActorPerturbArgs), P], C.c_int),
+        "lnw_policy_act_pop": ([C.POINTER(PolicyArgs), C.POINTER(PolicyPop), P], C.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)

@@ -6,8 +6,9 @@ rows as the sequence), ppo.py:716-729 (popart_normalize), ppo.py:342-362 (the
 two losses), ppo.py:371-380 (clip_grad_norm_ and Adam per network),
 ppo.py:311-319 (the prioritised sampler). The kernels are csrc/lnw_ppolearn.hip
 (lnw_ppo_grad, lnw_ppo_clip_adam). learn()'s outer schedule (noise ratio, lr
-halving on victories, epoch count), parameter noise and red-side training stay
-with the caller.
+halving on victories, epoch count) and red-side training stay with the caller;
+parameter noise is the rollout's (lnw.rollout.Rollout(param_noise=..., theta=
+learner.theta_actor) acts from this learner's flat vector).
 """
 import ctypes as C
 

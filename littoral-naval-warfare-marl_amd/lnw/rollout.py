@@ -232,15 +232,109 @@ def keyed_normal(row0, rows, cols, seed, slot, device):
     slot * 2^40 + row * 2 * cols + k, then Box-Muller. A rank holding global
     envs [lo, hi) draws exactly the values one rank holding all envs draws for
     them, so a sharded rollout samples what an unsharded one does."""
+    u = keyed_uniform(row0, rows, cols, seed, slot, device)
+    r = torch.sqrt(-2.0 * torch.log1p(-u[:, :cols]))  # 1 - u in (0, 1]
+    return r * torch.cos((2.0 * np.pi) * u[:, cols:])
+
+
+def keyed_uniform(row0, rows, cols, seed, slot, device):
+    """The uniforms [rows, 2 cols] under keyed_normal's draws: row r holds the
+    Philox stream's values at slot * 2^40 + (row0 + r) * 2 * cols + k (radii for
+    k < cols, then angles). The fill starts at a multiple of 4 (one Philox block
+    holds four values); an offset that is none (row0 * 2 * cols odd pairs: the
+    parameter-noise rows, cols = the flat actor size) is filled from the block
+    below and cut."""
     from . import _abi
     L = _abi.load()
     per = 2 * cols
-    u = torch.empty((rows, per), dtype=torch.float32, device=device)
     off = (int(slot) << 40) + int(row0) * per
-    _abi.check(L.lnw_fill_uniform_f32(u.data_ptr(), rows * per, int(seed), off,
+    lead = off & 3
+    u = torch.empty(lead + rows * per, dtype=torch.float32, device=device)
+    _abi.check(L.lnw_fill_uniform_f32(u.data_ptr(), u.numel(), int(seed), off - lead,
                                       torch.cuda.current_stream(device).cuda_stream))
-    r = torch.sqrt(-2.0 * torch.log1p(-u[:, :cols]))  # 1 - u in (0, 1]
-    return r * torch.cos((2.0 * np.pi) * u[:, cols:])
+    return u[lead:].reshape(rows, per)
+
+
+# ---- parameter noise (ppo.py:452-482): flat and packed actor vectors -----------
+# The flat layout is the learner's (ppolearn.actor_slices, include/lnw.h), the
+# packed one what lnw_policy_act reads (BatchedActor.packed_policy()).
+NOISE_FREE = ("norm1", "norm2", "layernorm")  # name parts the reference leaves alone (ppo.py:470-473)
+
+
+def _flat_layout(n_in):
+    from .ppolearn import actor_slices, flat_size  # (ppolearn imports this module)
+    sl = actor_slices(n_in)
+    return sl, flat_size(sl)
+
+
+def flat_n_in(P):
+    """n_in of a flat actor vector of P floats (P = 7139 + 66 n_in)."""
+    n_in, rem = divmod(int(P) - 7139, 66)
+    if rem or n_in < 12:
+        raise ValueError(f"{P} floats is no flat actor vector")
+    return n_in
+
+
+def noise_mask(n_in, device=None):
+    """float32 [P], 1 where parameter noise is added, in the flat layout: every
+    weight and bias of conv1, conv2, convhead, fc1, fc2, fc3 and the two heads; 0
+    on norm1.*, norm2.* (running statistics included), layernorm.* and the logstd
+    slot (which the reference noises, and nothing reads)."""
+    sl, P = _flat_layout(n_in)
+    m = torch.zeros(P, dtype=torch.float32)
+    for name, (k, shp) in sl.items():
+        if name != "logstd" and not any(s in name for s in NOISE_FREE):
+            m[k:k + int(np.prod(shp))] = 1.0
+    return m.to(device) if device is not None else m
+
+
+def unpack_policy(packed, n_in):
+    """The inverse of BatchedActor.packed_policy(): packed sets [..., floats] to
+    flat vectors [..., P], bit for bit (hi + mid + lo of a weight's three
+    bfloat16 terms is exact in float32). The logstd slot, which the packed set
+    does not hold, is 0."""
+    sl, P = _flat_layout(n_in)
+    x = packed.reshape(-1, packed.shape[-1])
+    M = x.shape[0]
+    out = torch.zeros((M, P), dtype=torch.float32, device=x.device)
+    n_par = 578 + 2 * n_in
+    out[:, :n_par] = x[:, :n_par]
+    o = (n_par + 3) & ~3
+    for name, cnt in (("fc1.bias", 64), ("fc2.bias", 64), ("fc3.bias", 32)):
+        out[:, sl[name][0]:sl[name][0] + cnt] = x[:, o:o + cnt]
+        o += cnt
+    for name, k_pad, n_pad, rows, cols in (("fc1.weight", 32 if n_in <= 32 else 64, 64, 64, n_in),
+                                           ("fc2.weight", 64, 64, 64, 64), ("fc3.weight", 64, 32, 32, 64),
+                                           ("normal_head.weight", 32, 16, 8, 32)):  # (+ log_std_head, adjacent)
+        nt, qp = n_pad // 16, k_pad // 32
+        cnt = 3 * nt * qp * 64 * 4
+        pl = x[:, o:o + cnt].contiguous().view(torch.bfloat16).reshape(M, 3, nt, qp, 64, 8).float()
+        o += cnt
+        w = (pl[:, 0] + pl[:, 1]) + pl[:, 2]
+        # [nt][p][lane = 16 g + m][j = 4 half + v] -> [nt][m][p][half][g][v]
+        w = w.reshape(M, nt, qp, 4, 16, 2, 4).permute(0, 1, 4, 2, 5, 3, 6).reshape(M, n_pad, k_pad)
+        out[:, sl[name][0]:sl[name][0] + rows * cols] = w[:, :rows, :cols].reshape(M, -1)
+    return out.reshape(packed.shape[:-1] + (P,))
+
+
+def perturbed_theta(theta, member0, members, std, clip, seed, call, T, dtype=torch.float32):
+    """What lnw_actor_perturb computes, restated with torch ops: the flat vectors
+    [members, P] of population members member0 .. member0 + members - 1,
+    theta_m = theta + mask * clamp(std * z_m, -clip, +clip) (ppo.py:474-475) with
+    z_m = keyed_normal(row0 = m, rows = 1, cols = P, seed, slot = call * T * 4 + 3):
+    slot 3 of the rollout's first step, which no action draw uses (0: blue
+    sample, 1: blue action noise, 2: red sample). std == 0 returns theta itself.
+    dtype=torch.float64 evaluates the same uniforms in double (tests)."""
+    theta = theta.reshape(-1)
+    P = theta.numel()
+    base = theta.to(dtype)[None].expand(members, P)
+    if float(std) == 0.0:
+        return base.clone()
+    mask = noise_mask(flat_n_in(P), theta.device) != 0
+    u = keyed_uniform(member0, members, P, seed, (int(call) * int(T)) * 4 + 3, theta.device).to(dtype)
+    z = torch.sqrt(-2.0 * torch.log1p(-u[:, :P])) * torch.cos((2.0 * np.pi) * u[:, P:])
+    nz = torch.clamp(std * z, -clip, clip)
+    return base + torch.where(mask[None], nz, torch.zeros((), dtype=dtype, device=theta.device))
 
 
 def red_script_table(device="cuda", dtype=torch.float64):
@@ -349,9 +443,12 @@ class Rollout:
     Differences from the reference loop, by design:
       * it observes the env it steps; ppo.py:497 calls get_obs on self.env, a
         Game that rollout() never steps (a reference bug, SURVEY.md §3.3);
-      * exploration: the reference's parameter noise and adaptive noise ratio
-        (ppo.py:466-482, 586-596) belong to the learner; `noise` adds a fixed
-        N(0, noise) term like MLP.forward's `noise` argument;
+      * exploration: `noise` adds a fixed N(0, noise) term like MLP.forward's
+        `noise` argument; parameter noise is below; the noise ratio's schedule
+        and its in-rollout adaptation (ppo.py:586-596) stay with the caller;
+      * a noised actor whose heads are NaN for a row acts N(0, 1) for that row
+        (lnw_policy_act's guard); the reference reloads the noiseless actor for
+        the rest of the episode (ppo.py:505-507);
       * sunk ships' action rows are stored as zeros (the reference stores the
         previous ship's `action` variable there, ppo.py:516-517).
 
@@ -369,15 +466,63 @@ class Rollout:
     `run(forced_actions=...)` replays given actor outputs [E, T, A, 4] instead of
     sampling (log-probabilities from get_dist): parity against recorded
     reference rollouts (tests/golden/make_rollout_golden.py).
+
+    Parameter noise (ppo.py:452-482, the reference's default exploration): a
+    population of noised actors inside one rollout. `envs_per_member=G` splits
+    the global envs into members of G consecutive envs (member m = global envs
+    [m G, (m + 1) G), so game.env_id_base must be a multiple of G); each member
+    acts for the whole rollout with its own copy of the blue actor, theta_m =
+    theta + mask * clamp(std * z_m, -clip, +clip) (perturbed_theta, noise_mask).
+    G = 1 is the reference: one noised actor per episode. The log-probabilities
+    returned are the noised actor's, the critic and the red actor are not noised.
+      * `param_noise=(std, clip)` creates `self.param_noise`, a float32 [2]
+        device tensor read on the device at every run: rewrite it in place
+        between runs and graph replays (std 0: no noise). Every run / replay
+        draws fresh noise (keyed by the seed, `call_index` and the global member).
+      * `theta`: the blue actor as a flat device vector in the learner's layout
+        (PPOLearner.theta_actor), read at run time, not copied: the rollout acts
+        from the learner's current weights with no export() and no repack by
+        torch ops. None: packed from the module, as without these arguments.
+      * `member_thetas` [M, P]: explicit per-member vectors (M >= the game's
+        members), no draws: parity against recorded reference actors.
+    The hip impl runs lnw_actor_perturb once per run (inside a captured graph
+    too) and every blue policy launch through lnw_policy_act_pop; the returned
+    buffers hold "member" [E] int64, the global member of each env. With none
+    of these arguments the rollout issues exactly the launches it did.
     """
 
     def __init__(self, game: BatchedGame, actor, critic=None, steps=40, red="script",
                  red_actor=None, noise=None, bn="sample", red_bn="running", gamma=0.99,
-                 stop_at_done=True, observe="fresh", keyed_seed=None, impl="hip", seed=0):
+                 stop_at_done=True, observe="fresh", keyed_seed=None, impl="hip", seed=0,
+                 param_noise=None, envs_per_member=None, theta=None, member_thetas=None):
         if observe not in ("fresh", "step"):
             raise ValueError("observe must be 'fresh' or 'step'")
         if impl not in ("hip", "torch"):
             raise ValueError("impl must be 'hip' or 'torch'")
+        if envs_per_member is None:
+            if param_noise is not None or member_thetas is not None:
+                raise ValueError("envs_per_member is required with param_noise or member_thetas")
+        else:
+            if param_noise is None and member_thetas is None:
+                raise ValueError("envs_per_member needs param_noise or member_thetas")
+            if int(envs_per_member) != envs_per_member or envs_per_member <= 0:
+                raise ValueError("envs_per_member must be a positive integer")
+            if game.env_id_base % int(envs_per_member):
+                raise ValueError("game.env_id_base must be a multiple of envs_per_member")
+        if member_thetas is not None and (param_noise is not None or theta is not None):
+            raise ValueError("member_thetas excludes param_noise and theta")
+        if param_noise is not None:
+            if len(param_noise) != 2 or not (param_noise[0] >= 0 and param_noise[1] >= 0):
+                raise ValueError("param_noise must be (std >= 0, clip >= 0)")
+        self.G = int(envs_per_member) if envs_per_member is not None else None
+        self.theta, self.member_thetas = theta, member_thetas
+        n_members = -(-game.E // self.G) if self.G else 1
+        if member_thetas is not None and (member_thetas.dim() != 2 or member_thetas.shape[0] < n_members):
+            raise ValueError(f"member_thetas must be [M >= {n_members}, P]")
+        self.param_noise = None
+        if param_noise is not None:
+            self.param_noise = torch.tensor([float(param_noise[0]), float(param_noise[1])],
+                                            dtype=torch.float32, device=game.device)
         self.keyed_seed, self.impl, self.seed = keyed_seed, impl, int(seed)
         self.g, self.actor, self.critic = game, actor, critic
         self.T, self.red, self.red_actor = int(steps), red, red_actor
@@ -428,6 +573,48 @@ class Rollout:
                     running=(torch.ones if fill else torch.empty)((E, T), dtype=torch.bool, device=dev),
                     f32_step=z((E, T), dtype=torch.bool, device=dev))
 
+    def _flat_source(self):
+        """The flat actor vector(s) of this run on the game's device: the
+        explicit member vectors [M, P], else `theta` [P] as it stands now, else
+        the module's parameters packed into the flat layout."""
+        from .ppolearn import pack
+        dev = self.g.device
+        sl, P = _flat_layout(self.actor.layernorm.normalized_shape[0])
+        if self.member_thetas is not None:
+            src = self.member_thetas.to(device=dev, dtype=torch.float32).contiguous()
+        elif self.theta is not None:
+            src = self.theta
+            if src.dtype != torch.float32 or src.device != dev or not src.is_contiguous() or src.dim() != 1:
+                raise ValueError("theta must be a contiguous float32 vector on the game's device")
+        else:
+            src = pack(self.actor, sl).to(dev)
+        if src.shape[-1] != P:
+            raise ValueError(f"the flat actor vector holds {P} floats, not {src.shape[-1]}")
+        return src
+
+    def _member_actors(self, seed):
+        """torch impl: None, or (G, the members' actors as modules) — scratch
+        copies of the blue actor loaded from the members' flat vectors."""
+        import copy
+        if self.G is None and self.theta is None:
+            return None
+        g = self.g
+        G = self.G if self.G else g.E
+        M = -(-g.E // G)
+        src = self._flat_source()
+        if src.dim() == 1:
+            std, clip = self.param_noise.tolist() if self.param_noise is not None else (0.0, 0.0)
+            src = perturbed_theta(src, g.env_id_base // G, M, std, clip, seed, int(self._call.item()), self.T)
+        sl, _ = _flat_layout(self.actor.layernorm.normalized_shape[0])
+        actors = []
+        for k in range(M):
+            net = copy.deepcopy(self.actor)
+            sd = net.state_dict()  # (tensors sharing the copy's storage)
+            for name, (o, shp) in sl.items():
+                sd[name].copy_(src[k, o:o + int(np.prod(shp))].reshape(shp))
+            actors.append(net)
+        return G, actors
+
     def _run_hip(self, forced_actions, on_step):
         import ctypes as C
         from . import _abi
@@ -443,7 +630,30 @@ class Rollout:
         kinds = torch.full((E, A), _abi.LNW_KIND_F64, dtype=torch.uint8, device=dev)
         live = torch.ones(E, dtype=torch.bool, device=dev)
         red_actor_rows = self.red != "script" and self.red_actor is not None
-        ap = self.actor.packed_policy()
+        seed = int(self.keyed_seed if self.keyed_seed is not None else self.seed) & (2**64 - 1)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        pop = None
+        if self.G is not None or self.theta is not None:
+            # the members' packed sets [M, floats] from the flat vector(s), on the device
+            src = self._flat_source()
+            M = -(-E // self.G) if self.G else 1
+            floats = int(L.lnw_policy_packed_floats(Db))
+            if floats <= 0:
+                raise _abi.LnwError(f"the policy kernel does not support rows of {Db} floats")
+            ap = torch.empty((M, floats), dtype=torch.float32, device=dev)
+            pt = _abi.ActorPerturbArgs()
+            pt.theta, pt.theta_member_stride = src.data_ptr(), (src.shape[1] if src.dim() == 2 else 0)
+            pt.D, pt.T = Db, T
+            pt.member0, pt.members = (g.env_id_base // self.G if self.G else 0), M
+            pt.packed_out, pt.member_stride = ap.data_ptr(), floats
+            pt.noise_dev = self.param_noise.data_ptr() if self.param_noise is not None else None
+            pt.seed, pt.call_dev = seed, self._call.data_ptr()
+            _abi.check(L.lnw_actor_perturb(C.byref(pt), stream))
+            if self.G is not None:
+                pop = _abi.PolicyPop(self.G, floats)
+                b["member"] = torch.arange(E, dtype=torch.int64, device=dev) // self.G + pt.member0
+        else:
+            ap = self.actor.packed_policy()
         cp = self.critic.packed(nb, Db) if self.critic is not None else None
         if cp is None:  # (no critic: nothing writes the values, which are zeros)
             val.zero_()
@@ -456,8 +666,6 @@ class Rollout:
         if self.record_actions:
             b["step_actions"] = torch.zeros((E, T, A, 4), dtype=torch.float64, device=dev)
             b["step_kinds"] = torch.zeros((E, T, A), dtype=torch.uint8, device=dev)
-        seed = int(self.keyed_seed if self.keyed_seed is not None else self.seed) & (2**64 - 1)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         P = lambda t_: t_.data_ptr()  # noqa: E731
         f4, f8 = 4, 8
         table = self.table.contiguous() if self.table is not None else None
@@ -500,7 +708,10 @@ class Rollout:
                 pa.script_own0, pa.script_cnt = nb, nr
             pa.kinds, pa.kinds_f32_all_alive = P(kinds), int(red_actor_rows)
             pa.f32_out, pa.f32_env_stride = P(f32s) + t, T
-            _abi.check(L.lnw_policy_act(C.byref(pa), stream))
+            if pop is not None:
+                _abi.check(L.lnw_policy_act_pop(C.byref(pa), C.byref(pop), stream))
+            else:
+                _abi.check(L.lnw_policy_act(C.byref(pa), stream))
             if red_actor_rows:
                 ra = PolicyArgs()
                 ra.obs, ra.E, ra.n, ra.D, ra.own0, ra.A = P(g.obs_red), E, nr, Dr, nb, A
@@ -555,6 +766,21 @@ class Rollout:
             slot = ((int(call.item()) * T + t) * 4 + which)
             return keyed_normal(base * n_side, E * n_side, 4, self.keyed_seed, slot, dev)
 
+        # the blue actor of every row: the module, or each member's own copy
+        # for the member's rows (a population / a flat `theta`)
+        members = self._member_actors(int(self.keyed_seed if self.keyed_seed is not None else self.seed))
+
+        def blue(fn, *rows):
+            """fn(actor, *rows) -> tuple of [rows, ...] tensors, over the members"""
+            if members is None:
+                return fn(self.actor, *rows)
+            Gm, nets = members
+            parts = [fn(net, *[None if x is None else x[k * Gm * nb:(k + 1) * Gm * nb] for x in rows])
+                     for k, net in enumerate(nets)]
+            return tuple(torch.cat(c) for c in zip(*parts))
+
+        if self.G is not None:
+            b["member"] = torch.arange(E, dtype=torch.int64, device=dev) // self.G + base // self.G
         for t in range(T):
             if self.observe == "fresh":
                 g.observe(-1)
@@ -568,12 +794,13 @@ class Rollout:
                 if self.stop_at_done else cur
             if forced_actions is not None:
                 a = forced_actions[:, t, :nb].to(torch.float32)
-                lp, _ = self.actor.get_dist(cur.reshape(E * nb, D), a.reshape(E * nb, 4),
-                                            bn=self.bn)
+                lp, _ = blue(lambda net, x, fa: net.get_dist(x, fa, bn=self.bn),
+                             cur.reshape(E * nb, D), a.reshape(E * nb, 4))
             else:
-                a, lp, _ = self.actor(cur.reshape(E * nb, D), noise=self.noise, bn=self.bn,
-                                      generator=generator, eps=draws(t, 0, nb),
-                                      noise_eps=draws(t, 1, nb) if self.noise is not None else None)
+                a, lp, _ = blue(lambda net, x, eps, neps: net(x, noise=self.noise, bn=self.bn, generator=generator,
+                                                              eps=eps, noise_eps=neps),
+                                cur.reshape(E * nb, D), draws(t, 0, nb),
+                                draws(t, 1, nb) if self.noise is not None else None)
             a = torch.where(ab, a.reshape(E, nb, 4), torch.zeros((), device=dev))
             acts[:, t] = torch.where(keep, a, torch.zeros((), device=dev))
             logp[:, t] = torch.where(keep, lp.reshape(E, nb, 4), torch.zeros((), device=dev))

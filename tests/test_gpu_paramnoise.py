@@ -1,0 +1,444 @@
+"""Parameter-noise exploration on the GPU (ppo.py:452-482): lnw_actor_perturb
+(the members' packed parameter sets from the flat actor vector, with keyed
+noise), lnw_policy_act_pop (one policy launch over a population of actors) and
+lnw.rollout.Rollout(param_noise=..., envs_per_member=..., theta=...,
+member_thetas=...), against the torch restatements (perturbed_theta,
+unpack_policy, the torch rollout arm), against lnw_policy_act member by member,
+and against a recorded reference rollout (tests/golden/rollout_paramnoise.npz,
+written by tests/golden/make_paramnoise_golden.py)."""
+import ctypes as C
+import json
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "littoral-naval-warfare-marl_amd"))
+
+pytestmark = pytest.mark.gpu
+
+REF_BLUE = [(6, 61), (10, 81), (8, 70), (11, 58)]
+REF_RED = [(98, 48), (98, 52), (98, 56), (96, 52)]
+NAMES = {0: "small", 1: "large", 2: "ls"}
+
+
+def bits(t):
+    return t.contiguous().view(torch.uint8)
+
+
+def _actor(D, seed):
+    """An actor with every parameter and running statistic away from its
+    initial value (BatchNorm / LayerNorm affines, running statistics)."""
+    from lnw.rollout import BatchedActor
+    torch.manual_seed(seed)
+    a = BatchedActor.for_obs(D).cuda()
+    with torch.no_grad():
+        for m in (a.norm1, a.norm2):
+            m.running_mean.uniform_(-0.2, 0.2)
+            m.running_var.uniform_(0.5, 2.0)
+            m.weight.uniform_(0.5, 1.5)
+            m.bias.uniform_(-0.1, 0.1)
+        a.layernorm.weight.uniform_(0.5, 1.5)
+        a.layernorm.bias.uniform_(-0.1, 0.1)
+    return a
+
+
+def _flat(actor):
+    from lnw.ppolearn import actor_slices, pack
+    return pack(actor, actor_slices(actor.layernorm.normalized_shape[0])).cuda()
+
+
+def _perturb(theta, D, member0, members, noise=None, seed=0, call=0, T=5):
+    """lnw_actor_perturb -> packed sets [members, floats]; theta [P], or [members, P]
+    (each member its own vector); noise: None (noise_dev NULL) or (std, clip)."""
+    from lnw import _abi
+    L = _abi.load()
+    floats = int(L.lnw_policy_packed_floats(D))
+    out = torch.full((members, floats), float("nan"), device="cuda")
+    nz = torch.tensor(noise, dtype=torch.float32, device="cuda") if noise is not None else None
+    cd = torch.tensor([call], dtype=torch.int64, device="cuda")
+    a = _abi.ActorPerturbArgs()
+    a.theta, a.theta_member_stride = theta.data_ptr(), (theta.shape[1] if theta.dim() == 2 else 0)
+    a.D, a.T, a.member0, a.members = D, T, member0, members
+    a.packed_out, a.member_stride = out.data_ptr(), floats
+    a.noise_dev = nz.data_ptr() if nz is not None else None
+    a.seed, a.call_dev = seed, cd.data_ptr()
+    _abi.check(L.lnw_actor_perturb(C.byref(a), None))
+    torch.cuda.synchronize()
+    return out
+
+
+# ---- 1. exact repack -----------------------------------------------------------
+@pytest.mark.parametrize("D", [68, 84])  # n_in 31 (weights in LDS) and 47 (the 64-wide kernel)
+def test_exact_repack(D):
+    from lnw.rollout import unpack_policy
+    a = _actor(D, 1)
+    n_in = D - 37
+    want = a.packed_policy()
+    theta = _flat(a)
+    assert want.numel() == _perturb(theta, D, 0, 1).shape[1]
+    for noise in (None, (0.0, 0.05)):
+        got = _perturb(theta, D, 0, 3, noise=noise, seed=5, call=3)
+        for k in range(3):
+            assert torch.equal(bits(got[k]), bits(want)), (noise, k)
+    # each member from its own vector
+    got = _perturb(theta[None].repeat(3, 1).contiguous(), D, 4, 3)
+    assert torch.equal(bits(got), bits(want[None].expand(3, -1)))
+    assert torch.equal(bits(unpack_policy(want, n_in)), bits(theta))
+
+
+# ---- 2, 3. the noise values ----------------------------------------------------
+@pytest.mark.parametrize("D", [68, 84])
+@pytest.mark.parametrize("std,clip", [(0.5, 0.05), (0.01, 0.05)])
+def test_noise_values(std, clip, D):
+    """theta_m out of the packed sets against perturbed_theta evaluated in
+    float64 from the same uniforms. Masked entries are theta bit for bit;
+    entries where |std z| exceeds clip by more than 1e-5 std are float32(theta
+    +- clip) exactly; all others lie within 1e-5 std + 2^-23 max(|theta|, clip):
+    1e-5 is the error accepted on a keyed draw scaled by a std of order 1
+    (tests/test_gpu_rollout.py, keyed sampling), scaled here by std, plus one
+    float32 rounding of the sum."""
+    from lnw.rollout import keyed_uniform, noise_mask, perturbed_theta, unpack_policy
+    a = _actor(D, 2)
+    n_in = D - 37
+    theta = _flat(a)
+    P = theta.numel()
+    M, member0, seed, call, T = 5, 7, 1234, 2, 6
+    s32, c32 = float(np.float32(std)), float(np.float32(clip))
+    got = unpack_policy(_perturb(theta, D, member0, M, noise=(std, clip), seed=seed, call=call, T=T), n_in)
+    u = keyed_uniform(member0, M, P, seed, call * T * 4 + 3, "cuda").double()
+    nz = s32 * torch.sqrt(-2.0 * torch.log1p(-u[:, :P])) * torch.cos((2.0 * np.pi) * u[:, P:])
+    mask = (noise_mask(n_in, "cuda") != 0)[None].expand(M, P)
+    want = theta.double()[None] + torch.where(mask, nz.clamp(-c32, c32), 0.0)
+    torch.testing.assert_close(perturbed_theta(theta, member0, M, s32, c32, seed, call, T, dtype=torch.float64),
+                               want, rtol=0, atol=1e-12)
+    th = theta[None].expand(M, P)
+    assert torch.equal(bits(got[~mask]), bits(th[~mask]))
+    sat = mask & (nz.abs() > c32 + 1e-5 * s32)
+    edge = th + torch.where(nz > 0, c32, -c32).float()  # float32(theta +- clip)
+    assert torch.equal(bits(got[sat]), bits(edge[sat]))
+    rest = mask & ~sat
+    bound = 1e-5 * s32 + 2.0 ** -23 * torch.maximum(th.abs().double(), torch.tensor(c32, device="cuda").double())
+    err = (got.double() - want).abs()
+    print(f"std {std}: saturated {int(sat.sum())} of {int(mask.sum())}, largest error of the others "
+          f"{float(err[rest].max()):.3e} (bound >= {float(bound[rest].min()):.3e})")
+    assert bool((err[rest] <= bound[rest]).all())
+    if std > clip:  # (only draws with |z| < 0.1 stay inside the clamp)
+        assert int(sat.sum()) > 0.9 * int(mask.sum()) and int(rest.sum()) > 100
+    else:
+        assert int(sat.sum()) == 0
+    # the members differ from each other and from theta
+    assert not torch.equal(got[0], got[1]) and not torch.equal(got[0], theta)
+
+
+# ---- 4. shard invariance of the draws --------------------------------------------
+def test_draws_shard_invariant():
+    D = 68
+    theta = _flat(_actor(D, 3))
+    kw = dict(noise=(0.01, 0.05), seed=77, T=6)
+    whole = _perturb(theta, D, 0, 5, call=4, **kw)
+    parts = torch.cat([_perturb(theta, D, 0, 2, call=4, **kw), _perturb(theta, D, 2, 3, call=4, **kw)])
+    assert torch.equal(bits(whole), bits(parts))
+    assert torch.equal(bits(whole), bits(_perturb(theta, D, 0, 5, call=4, **kw)))
+    assert not torch.equal(whole, _perturb(theta, D, 0, 5, call=5, **kw))
+
+
+# ---- 5. the population launch = per-member launches ---------------------------------
+def _policy_case(n, D, G, E, forced, seed):
+    """Inputs of a policy launch over E envs of n ships (+ 2 scripted red), some
+    ships dead, some envs not live; and the members' noised sets."""
+    gen = torch.Generator(device="cuda").manual_seed(seed)
+    A = n + 2
+    obs = torch.rand((E, n, D), generator=gen, device="cuda")
+    obs[:, :, :49] = torch.randint(0, 256, (E, n, 49), generator=gen, device="cuda") / 255.0
+    alive = (torch.rand((A, E), generator=gen, device="cuda") > 0.15).to(torch.uint8)
+    live = (torch.rand(E, generator=gen, device="cuda") > 0.2).to(torch.uint8)
+    fa = torch.rand((E, A, 4), generator=gen, device="cuda")
+    script = torch.rand((3, 40, 4), generator=gen, device="cuda", dtype=torch.float64)
+    M = -(-E // G)
+    sets = _perturb(_flat(_actor(D, seed)), D, 3, M, noise=(0.5, 0.05), seed=seed, call=1)
+    return dict(n=n, D=D, G=G, E=E, A=A, forced=forced, obs=obs, alive=alive, live=live, fa=fa, script=script,
+                sets=sets, M=M)
+
+
+def _launch(c, lo, hi, out, pop):
+    """One policy launch on envs [lo, hi) of case c into the buffers `out`: the
+    population launch (pop) or lnw_policy_act with the set of lo's member."""
+    from lnw import _abi
+    L = _abi.load()
+    n, D, A, E = c["n"], c["D"], c["A"], c["E"]
+    alive = c["alive"][:, lo:hi].contiguous()  # [A][hi - lo]
+    call = torch.tensor([2], dtype=torch.int64, device="cuda")
+    pa = _abi.PolicyArgs()
+    pa.obs, pa.E, pa.n, pa.D, pa.own0, pa.A = c["obs"][lo:].data_ptr(), hi - lo, n, D, 0, A
+    pa.params = c["sets"][lo // c["G"]].data_ptr()
+    if c["forced"]:
+        pa.forced, pa.forced_act, pa.fa_env_stride = 1, c["fa"][lo:].data_ptr(), A * 4
+    pa.noise, pa.seed, pa.call_dev, pa.T, pa.t, pa.which = 0.05, 99, call.data_ptr(), 7, 3, 0
+    pa.row_base = (1000 + lo) * n
+    pa.alive, pa.live = alive.data_ptr(), c["live"][lo:].data_ptr()
+    pa.obs_out, pa.obs_env_stride = out["obs"][lo:].data_ptr(), n * D
+    pa.act_out, pa.logp_out, pa.act_env_stride = out["act"][lo:].data_ptr(), out["logp"][lo:].data_ptr(), n * 4
+    pa.full = out["full"][lo:].data_ptr()
+    pa.script, pa.script_n, pa.script_steps, pa.script_own0, pa.script_cnt = c["script"].data_ptr(), 3, 40, n, 2
+    pa.kinds, pa.kinds_f32_all_alive = out["kinds"][lo:].data_ptr(), 1
+    pa.f32_out, pa.f32_env_stride = out["f32"][lo:].data_ptr(), 1
+    if pop:
+        pp = _abi.PolicyPop(c["G"], c["sets"].shape[1])
+        _abi.check(L.lnw_policy_act_pop(C.byref(pa), C.byref(pp), None))
+    else:
+        _abi.check(L.lnw_policy_act(C.byref(pa), None))
+    torch.cuda.synchronize()
+
+
+def _outputs(c):
+    n, D, A, E = c["n"], c["D"], c["A"], c["E"]
+    return dict(obs=torch.full((E, n, D), -1.0, device="cuda"), act=torch.full((E, n, 4), -1.0, device="cuda"),
+                logp=torch.full((E, n, 4), -1.0, device="cuda"),
+                full=torch.full((E, A, 4), -1.0, dtype=torch.float64, device="cuda"),
+                kinds=torch.full((E, A), 9, dtype=torch.uint8, device="cuda"),
+                f32=torch.full((E,), 9, dtype=torch.uint8, device="cuda"))
+
+
+@pytest.mark.parametrize("forced", [False, True])
+@pytest.mark.parametrize("n,D,G,E", [
+    (4, 68, 3, 4 * 3 + 2),        # blocks nearly empty
+    (4, 68, 128, 4 * 128 + 7),    # exactly one block per member
+    (4, 68, 129, 4 * 129 + 7),    # a member's second block holds 4 rows
+    (8, 84, 3, 4 * 3 + 2),
+    (8, 84, 128, 4 * 128 + 7),    # two full blocks per member
+    (8, 84, 129, 4 * 129 + 7),    # a third block of 8 rows
+])
+def test_population_launch_equals_member_launches(n, D, G, E, forced):
+    c = _policy_case(n, D, G, E, forced, seed=11 + n + G)
+    assert E % G and c["M"] == 5
+    pop = _outputs(c)
+    _launch(c, 0, E, pop, True)
+    one = _outputs(c)
+    for k in range(c["M"]):
+        _launch(c, k * G, min((k + 1) * G, E), one, False)
+    for key in pop:
+        assert torch.equal(bits(pop[key]), bits(one[key])), key
+    again = _outputs(c)
+    _launch(c, 0, E, again, True)
+    for key in pop:
+        assert torch.equal(bits(pop[key]), bits(again[key])), key
+    # the members' sets matter: member 1's rows differ under member 0's set
+    if not forced:
+        c2 = dict(c, sets=c["sets"][:1].expand(c["M"], -1).contiguous())
+        same = _outputs(c2)
+        _launch(c2, 0, E, same, True)
+        assert torch.equal(bits(same["act"][:G]), bits(pop["act"][:G]))
+        assert not torch.equal(same["act"][G:], pop["act"][G:])
+
+
+# ---- 6 - 9. rollouts ---------------------------------------------------------------
+def _game(E, seed=8, base=0, f64=True):
+    from lnw.batched import BatchedGame
+    from lnw.config import Scenario
+    sc = Scenario(landing_ops=False, trained_red=False, auto_reset=False)
+    g = BatchedGame(E, ["small"] * 4, ["large"] * 4, scenario=sc, seed=seed, env_id_base=base,
+                    reward_dtype=torch.float64 if f64 else torch.float32)
+    g.set_variant(True)
+    g.reset(positions=REF_BLUE + REF_RED, box=((40, 40), (57, 65)))
+    return g
+
+
+def _nets(seed=4):
+    from lnw.rollout import BatchedCritic
+    actor = _actor(68, seed)
+    critic = BatchedCritic(68 * 4).cuda()
+    return actor, critic
+
+
+@pytest.mark.parametrize("std,clip", [(0.5, 0.05), (0.01, 0.05)])
+def test_rollout_hip_matches_torch_arm(std, clip):
+    """The method and tolerances of test_fused_rollout_matches_torch_impl, with a
+    population: forced actor outputs (both arms step the same envs), then one
+    step of keyed sampling."""
+    from lnw.rollout import Rollout
+    E, G, T = 64, 16, 5
+    actor, critic = _nets()
+    forced = torch.rand((E, T, 8, 4), generator=torch.Generator(device="cuda").manual_seed(3), device="cuda")
+    outs = {}
+    for impl in ("hip", "torch"):
+        g = _game(E)
+        r = Rollout(g, actor, critic, steps=T, impl=impl, seed=31, param_noise=(std, clip), envs_per_member=G)
+        r.call_index(2)
+        outs[impl] = {k: v.clone() for k, v in r.run(forced_actions=forced).items()}
+        g.close()
+    h, t = outs["hip"], outs["torch"]
+    for k in ("obs", "actions", "running", "rewards", "f32_step", "rtg", "member"):
+        assert torch.equal(h[k], t[k]), k
+    assert h["member"].dtype == torch.int64
+    assert torch.equal(h["member"].cpu(), torch.arange(E) // G)
+    torch.testing.assert_close(h["log_probs"], t["log_probs"], rtol=0, atol=1e-4)
+    torch.testing.assert_close(h["values"], t["values"], rtol=0, atol=1e-5)
+    # the noise is there: other log-probabilities than the plain rollout's
+    g = _game(E)
+    plain = Rollout(g, actor, critic, steps=T, seed=31).run(forced_actions=forced)
+    assert float((plain["log_probs"] - h["log_probs"]).abs().max()) > 1e-3
+    g.close()
+    samp = {}
+    for impl in ("hip", "torch"):
+        g = _game(E, f64=False)
+        r = Rollout(g, actor, None, steps=1, impl=impl, keyed_seed=21, noise=0.05, param_noise=(std, clip),
+                    envs_per_member=G)
+        samp[impl] = {k: v.clone() for k, v in r.run().items()}
+        g.close()
+    torch.testing.assert_close(samp["hip"]["actions"], samp["torch"]["actions"], rtol=0, atol=1e-5)
+    torch.testing.assert_close(samp["hip"]["log_probs"], samp["torch"]["log_probs"], rtol=0, atol=1e-3)
+
+
+def test_sharded_rollout():
+    """A game holding members 2..3 (env_id_base = 2 G) reproduces those envs of
+    the unsharded rollout bit for bit."""
+    from lnw.rollout import Rollout
+    E, G, T = 64, 16, 5
+    actor, critic = _nets()
+    kw = dict(steps=T, keyed_seed=13, noise=0.05, param_noise=(0.5, 0.05), envs_per_member=G)
+    g = _game(E, seed=77)
+    r = Rollout(g, actor, critic, **kw)
+    r.call_index(3)
+    whole = {k: v.clone() for k, v in r.run().items()}
+    g.close()
+    g = _game(E - 2 * G, seed=77, base=2 * G)
+    r = Rollout(g, actor, critic, **kw)
+    r.call_index(3)
+    part = r.run()
+    assert torch.equal(part["member"].cpu(), torch.arange(2 * G, E) // G)
+    for k, v in whole.items():
+        assert torch.equal(bits(part[k]), bits(v[2 * G:])), k
+    g.close()
+
+
+def test_graph_replay_follows_param_noise():
+    from lnw.rollout import Rollout
+    E, G, T = 64, 16, 5
+    actor, critic = _nets()
+    g = _game(E, seed=5)
+    r = Rollout(g, actor, critic, steps=T, seed=99, param_noise=(0.5, 0.05), envs_per_member=G)
+    r.capture()
+
+    def replay(call):
+        g.set_state(snap)
+        r.call_index(call)
+        out = {k: v.clone() for k, v in r.replay().items()}
+        torch.cuda.synchronize()
+        return out
+
+    g.reset(positions=REF_BLUE + REF_RED, box=((40, 40), (57, 65)))
+    snap = g.get_state(device="cuda")
+    one, two = replay(7), replay(8)
+    assert r.call_index() == 9
+    assert torch.equal(one["obs"][:, 0], two["obs"][:, 0])
+    assert not torch.equal(one["actions"][:, 0], two["actions"][:, 0])
+    # the same rollout index again: the same noise and draws
+    again = replay(7)
+    for k, v in one.items():
+        assert torch.equal(bits(again[k]), bits(v)), k
+    # std = 0, written in place: the plain rollout at that rollout index
+    r.param_noise[0] = 0.0
+    quiet = replay(7)
+    g.set_state(snap)
+    p = Rollout(g, actor, critic, steps=T, seed=99)
+    p.call_index(7)
+    plain = p.run()
+    for k, v in plain.items():
+        assert torch.equal(bits(quiet[k]), bits(v)), k
+    assert not torch.equal(quiet["actions"], one["actions"])
+    g.close()
+
+
+def test_rollout_from_learner_vector():
+    """After one PPOLearner.step, Rollout(theta=learner.theta_actor) equals bit
+    for bit the rollout run after learner.export() from the modules."""
+    from lnw.ppolearn import PPOLearner
+    from lnw.rollout import Rollout
+    E, T = 8, 5
+    actor, critic = _nets()
+    g = _game(E, seed=3, f64=False)
+    snap = g.get_state(device="cuda")
+    first = Rollout(g, actor, critic, steps=T, stop_at_done=False, seed=5)
+    out = {k: v.clone() for k, v in first.run().items()}
+    learner = PPOLearner(actor, critic)
+    rtg = torch.randn((E, T, g.nb), generator=torch.Generator().manual_seed(1), dtype=torch.float64).cuda()
+    idx = learner.sample(out, 64, generator=torch.Generator(device="cuda").manual_seed(2), rtg=rtg)
+    before = learner.theta_actor.clone()
+    learner.step(learner.rows(out, idx, rtg=rtg))
+    assert not torch.equal(before, learner.theta_actor)
+    # from the vector, the modules still holding the old weights
+    g.set_state(snap)
+    r = Rollout(g, actor, critic, steps=T, stop_at_done=False, seed=5, theta=learner.theta_actor)
+    r.call_index(1)
+    vec = {k: v.clone() for k, v in r.run().items()}
+    learner.export()
+    g.set_state(snap)
+    r = Rollout(g, actor, critic, steps=T, stop_at_done=False, seed=5)
+    r.call_index(1)
+    mod = r.run()
+    for k in ("obs", "actions", "log_probs", "rewards", "running", "rtg"):
+        assert torch.equal(bits(vec[k]), bits(mod[k])), k
+    assert not torch.equal(vec["log_probs"], out["log_probs"])
+    g.close()
+
+
+# ---- 10. the reference pin ---------------------------------------------------------
+@pytest.mark.parametrize("impl", ["hip", "torch"])
+def test_reference_rollout_with_noised_actors(impl):
+    """tests/golden/rollout_paramnoise.npz: one reference PPO.rollout with
+    parameter noise (std 0.5, clip 0.05), replayed with G = 1, the recorded
+    per-episode actors as member_thetas and the recorded actions forced;
+    observations, rewards, values and log-probabilities as
+    tests/test_gpu_rollout_golden.py checks them."""
+    from _oracle import load_fixture
+    from lnw.batched import BatchedGame
+    from lnw.config import Scenario
+    from lnw.ppolearn import actor_slices
+    from lnw.rollout import BatchedActor, BatchedCritic, Rollout, noise_mask
+    fx = load_fixture("rollout_paramnoise.npz")
+    meta = json.loads(str(fx["meta"]))
+    eps, R, T, nb = meta["episodes"], meta["R"], meta["T"], meta["nb"]
+    types = eps[0]["types"]
+    grid = load_fixture("grids.npz")["grid100"]
+    sc = Scenario(landing_ops=False, trained_red=False, tactics="aggressive", side="blue", auto_reset=False)
+    g = BatchedGame(R, [NAMES[t] for t in types[:nb]], [NAMES[t] for t in types[nb:]], scenario=sc, grid=grid,
+                    reward_dtype=torch.float64)
+    tapes = [fx["tape"][e["tape_start"]:e["tape_end"]] for e in eps]
+    offs = np.concatenate([[0], np.cumsum([len(t) for t in tapes])]).astype(np.int64)
+    g.set_tape(np.concatenate(tapes), offs)
+    pos = np.array([e["spawn"] for e in eps], np.int32)
+    g.reset(positions=pos[0], rand_ls=[0] * len(types), pos_per_env=torch.from_numpy(pos))
+    n_in = g.Db - 37
+    sl = actor_slices(n_in)
+    actor = BatchedActor.for_obs(g.Db).load_reference(
+        {k[len("actor."):]: fx[k] for k in fx if k.startswith("actor.")}).cuda()
+    critic = BatchedCritic(g.Db * nb).load_reference(
+        {k[len("critic."):]: fx[k] for k in fx if k.startswith("critic.")}).cuda()
+    thetas = torch.from_numpy(np.concatenate([fx["ep_actor." + name].reshape(R, -1).astype(np.float32)
+                                              for name in sl], 1)).cuda()
+    theta0 = np.concatenate([fx["actor." + name].reshape(-1) for name in sl]).astype(np.float32)
+    mask = noise_mask(n_in).numpy() != 0
+    diff = np.abs(thetas.cpu().numpy() - theta0[None])
+    # |theta_ep - theta_0| <= clip as float32 states it: theta_ep = float32(theta_0 + noise)
+    # lies between float32(theta_0 - clip) and float32(theta_0 + clip)
+    c32 = np.float32(meta["clip"])
+    assert ((thetas.cpu().numpy() >= theta0[None] - c32) & (thetas.cpu().numpy() <= theta0[None] + c32)).all()
+    lg = sl["logstd"][0]  # (the reference noises logstd, which nothing reads: not in the mask)
+    assert (diff[:, ~mask & (np.arange(mask.size) != lg)] == 0).all() and (diff[:, mask] != 0).mean() > 0.99
+    r = Rollout(g, actor, critic, steps=T, red="script", gamma=meta["gamma"], impl=impl, envs_per_member=1,
+                member_thetas=thetas)
+    out = r.run(forced_actions=torch.from_numpy(fx["act"]).cuda())
+    torch.cuda.synchronize()
+    assert np.array_equal(out["running"].cpu().numpy().sum(1), meta["n_steps"])
+    assert np.array_equal(out["member"].cpu().numpy(), np.arange(R))
+    np.testing.assert_array_equal(out["obs"].cpu().numpy(), fx["batch_obs"])
+    np.testing.assert_allclose(out["rewards"].cpu().numpy(), fx["rew"], rtol=0, atol=1e-5)
+    np.testing.assert_allclose(out["log_probs"].cpu().numpy(), fx["batch_log_probs"], rtol=0, atol=1e-4)
+    vals = out["values"].cpu().numpy()
+    np.testing.assert_allclose(vals[:, :, None, None].repeat(nb, 2), fx["batch_values"], rtol=0, atol=1e-5)
+    np.testing.assert_allclose(out["rtg"].cpu().numpy(), fx["batch_rtg"][..., 0], rtol=1e-5, atol=1e-5)
+    g.close()
