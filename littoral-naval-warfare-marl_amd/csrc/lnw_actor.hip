@@ -28,7 +28,6 @@ namespace {
 
 using namespace lnw;
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 // the conv head (bn_relu, conv_head_win, conv_head_row, load_tail_q), its packed

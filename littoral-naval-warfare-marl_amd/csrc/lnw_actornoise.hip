@@ -23,8 +23,6 @@ namespace {
 
 using namespace lnw;
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 // the conv head block's layout (C1W .. CONV_PARAMS, obs_width_ok) and the two
 // parameter layouts (policy_pack, actor_flat)
 #include "lnw_convhead.inc"

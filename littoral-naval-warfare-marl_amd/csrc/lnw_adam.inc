@@ -1,7 +1,8 @@
 // lnw_adam.inc — one torch.optim.Adam step of one element (single-tensor
 // arithmetic, no weight decay), shared by lnw_qnet_adam (lnw_qlearn.hip) and
-// lnw_ppo_clip_adam (lnw_ppolearn.hip), and the hyperparameters' way across the
-// C-ABI. Included inside the sources' anonymous namespace.
+// lnw_ppo_clip_adam (lnw_ppolearn.hip), the hyperparameters' way across the
+// C-ABI and the two entry points' argument checks. Included inside the sources'
+// anonymous namespace.
 // The hyperparameters arrive as the doubles the caller meant (as_decimal): torch
 // forms 1 - beta, lr / (1 - beta1^t) and sqrt(1 - beta2^t) in double and rounds
 // each to float32 once.
@@ -31,4 +32,19 @@ inline double as_decimal(float x) {
     if (strtof(buf, nullptr) == x) return strtod(buf, nullptr);
   }
   return (double)x;
+}
+
+struct AdamHyper {
+  double lr, beta1, beta2, eps;
+};
+
+inline AdamHyper adam_hyper(float lr, float beta1, float beta2, float eps) {
+  return {as_decimal(lr), as_decimal(beta1), as_decimal(beta2), as_decimal(eps)};
+}
+
+// what both entry points ask of their arguments
+inline bool adam_args_ok(const float *params, const float *grad, const float *m, const float *v, int64_t count,
+                         const int64_t *step_dev, float lr, float beta1, float beta2, float eps) {
+  if (!params || !grad || !m || !v || !step_dev || count < 0) return false;
+  return lr >= 0.f && beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f;
 }

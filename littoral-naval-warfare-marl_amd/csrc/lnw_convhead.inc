@@ -2,10 +2,11 @@
 // share (network.py:70-82 MLP.forward, network.py:280-291 DMLP.forward): conv
 // 1->5 (3x3, pad 1) over the 7x7 terrain window, BatchNorm, ReLU, 2x2 max pool,
 // conv 5->8, BatchNorm, ReLU, 2x2 max pool, linear 8->12; one row per thread.
-// Included by lnw_actor.hip, lnw_qnet.hip and lnw_qlearn.hip inside their
-// anonymous namespace (after lnw_device.h: WAVE, and their f32x4 typedef); the
-// packed parameter layout below is what BatchedActor.packed_features() and
-// BatchedQNet.packed() write first.
+// Included by lnw_actor.hip, lnw_actornoise.hip, lnw_qnet.hip, lnw_qlearn.hip and
+// lnw_ppolearn.hip inside their anonymous namespace (after lnw_device.h: WAVE,
+// f32x4); the two learners include lnw_learn.inc behind it, which holds the
+// backward of this head. The packed parameter layout below is what
+// BatchedActor.packed_features() and BatchedQNet.packed() write first.
 
 constexpr int WIN = 49;       // 7x7 terrain window
 constexpr int MAX_IN = 64;    // bound of n_in = D - WIN + 12, the head's 12 outputs and the rest of the row
@@ -98,6 +99,19 @@ __device__ __forceinline__ void conv2_raw(const float *P, const float *pc, int s
   }
 }
 
+// 2x2 max pool (7x7 -> 3x3) of conv1's channel c into the thread's column pc of
+// a [45][stride] parking area
+__device__ __forceinline__ void pool1_park(const float (&v)[49], int c, float *pc, int stride) {
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+      const int r0 = 2 * i, c0 = 2 * j;
+      pc[(c * 9 + i * 3 + j) * stride] =
+          fmaxf(fmaxf(v[r0 * 7 + c0], v[r0 * 7 + c0 + 1]), fmaxf(v[(r0 + 1) * 7 + c0], v[(r0 + 1) * 7 + c0 + 1]));
+    }
+}
+
 // The conv head of one row (network.py:70-82): conv 1->5 over the 7x7 window
 // win[0..48] (registers) -> BN -> ReLU -> 2x2 pool, conv 5->8 -> BN -> ReLU ->
 // pool, folded into the linear 8->12 (h). P: packed parameters in LDS
@@ -117,15 +131,7 @@ __device__ __forceinline__ void conv_head_win(const float *P, const float (&win)
     float v[49];
     conv1_ch(P, win, c, v);
     bn_relu<49>(v, P + B1W, P + B1B, P + B1M, P + B1V, c, running);
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-      for (int j = 0; j < 3; j++) {
-        const int r0 = 2 * i, c0 = 2 * j;
-        pc[(c * 9 + i * 3 + j) * stride] =
-            fmaxf(fmaxf(v[r0 * 7 + c0], v[r0 * 7 + c0 + 1]),
-                  fmaxf(v[(r0 + 1) * 7 + c0], v[(r0 + 1) * 7 + c0 + 1]));
-      }
+    pool1_park(v, c, pc, stride);
   }
   // conv2 (5 -> 8, 3x3, pad 1) -> BN -> ReLU -> 2x2 max pool (3x3 -> 1x1),
   // folded straight into the linear 8 -> 12 (convhead), four output maps at a

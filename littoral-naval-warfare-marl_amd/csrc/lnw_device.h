@@ -12,6 +12,9 @@
 namespace lnw {
 
 constexpr int WAVE = 64;
+// native 4 x f32 vector: arrays of it stay in VGPRs (HIP's union-based float4
+// defeats SROA and lands such arrays in scratch)
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int R_MV = 4;           // move-table window: target offsets in [-4, 4]^2
 constexpr int MV_W = 2 * R_MV + 1;
 constexpr int MV_WORDS = 3;       // 81 bits per (class, start cell)

@@ -33,9 +33,6 @@
 
 using namespace lnw;
 
-// native 4 x f32 vector: arrays of it stay in VGPRs (HIP's union-based float4
-// defeats SROA and lands such arrays in scratch)
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x4_t __attribute__((ext_vector_type(4)));
 
 // One 16-B observation store at float4 index i4 of a wave-uniform base.

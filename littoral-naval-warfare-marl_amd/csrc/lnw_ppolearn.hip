@@ -52,15 +52,14 @@ namespace {
 
 using namespace lnw;
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 #include "lnw_convhead.inc"
+#include "lnw_learn.inc"
 #include "lnw_adam.inc"
 
-constexpr int PL_THREADS = 128;  // rows per workgroup of the per-row passes
-constexpr int PL_WAVES = PL_THREADS / WAVE;
-constexpr int PARK = 45 * PL_THREADS;  // pooled conv1 maps, one column per thread
-constexpr int LDW = 64;                // row stride of the actor's fc1 input (n_in <= 64, zero padded)
+constexpr int LDW = 64;  // row stride of the actor's fc1 input (n_in <= 64, zero padded)
+// the features pass's LDS copy of the parameters: the conv head and LayerNorm's w, b [n_in], padded to 8 floats
+constexpr int FEAT_LDS = (CONV_PARAMS + 2 * MAX_IN + 7) & ~7;
+static_assert(LDW == MAX_IN && FEAT_LDS == 712, "the kernels' LDS sizes are pinned by the resource tests");
 constexpr float LN_EPS = 1e-5f;
 constexpr int ADV_THREADS = 1024;
 constexpr int RUN_TAIL = 2048;  // 0.9^2048 of any float32 is below the smallest float32
@@ -70,12 +69,8 @@ constexpr int FC1 = 64, FC2 = 64, FC3 = 32, NHEAD = 8;
 // the critic's
 constexpr int CF1 = 32, CF2 = 64, CF3 = 64;
 
-// slab layouts (floats per workgroup) of the two conv passes
-constexpr int S4_C2W = 0, S4_C2B = 360, S4_B1W = 368, S4_B1B = 373, S4_HW = 378, S4_HB = 474, S4_B2W = 486,
-              S4_B2B = 494, S4_N = 502;
-constexpr int S5_C1W = 0, S5_C1B = 45, S5_N = 50;
-constexpr int CONV_SLABW = 504;
-enum { RED_CONV2 = 0, RED_CONV1 = 1 };
+// slab stride of the two conv passes (their layouts: lnw_learn.inc, S4 with its tail)
+constexpr int CONV_SLABW = (S4_N_TAIL + 3) & ~3;
 
 // per-row column fields [field][rows_pad] (floats and ints)
 constexpr int WS_V = 0, WS_DV = 1, WS_ADV = 2, WS_LNINV = 3, WS_DH = 4, WS_GY1 = 16, WS_POS1 = 61, WS_T = 66,
@@ -127,64 +122,7 @@ struct Ws {
 
 extern __shared__ float pl_lds[];
 
-// ---- reductions ------------------------------------------------------------
-__device__ __forceinline__ float dpp_add(float v, const int ctrl_sel) {
-  // (ctrl_sel is a compile-time constant at every call)
-  int x = __builtin_bit_cast(int, v), y;
-  switch (ctrl_sel) {
-    case 0: y = __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xf, 0xf, false); break;   // quad_perm [1,0,3,2]
-    case 1: y = __builtin_amdgcn_update_dpp(0, x, 0x4E, 0xf, 0xf, false); break;   // quad_perm [2,3,0,1]
-    case 2: y = __builtin_amdgcn_update_dpp(0, x, 0x141, 0xf, 0xf, false); break;  // row_half_mirror
-    default: y = __builtin_amdgcn_update_dpp(0, x, 0x140, 0xf, 0xf, false); break; // row_mirror
-  }
-  return v + __builtin_bit_cast(float, y);
-}
-
-// sum over the wave's 64 lanes in a fixed order (all lanes active), wave-uniform
-__device__ __forceinline__ float wave_sum(float v) {
-  v = dpp_add(v, 0);
-  v = dpp_add(v, 1);
-  v = dpp_add(v, 2);
-  v = dpp_add(v, 3);  // every lane: the sum of its row of 16
-  const int x = __builtin_bit_cast(int, v);
-  const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(x, 0));
-  const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(x, 16));
-  const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(x, 32));
-  const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(x, 48));
-  return (r0 + r1) + (r2 + r3);
-}
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-// the workgroup's sum of v into slot idx of its LDS staging [PL_WAVES][n]
-__device__ __forceinline__ void accum(float *wsl, int n, int idx, float v) {
-  const float s = wave_sum(v);
-  if ((threadIdx.x & (WAVE - 1)) == 0) wsl[(threadIdx.x / WAVE) * n + idx] = s;
-}
-
-__device__ __forceinline__ void flush(const float *wsl, int n, float *slab) {
-  __syncthreads();
-  for (int i = threadIdx.x; i < n; i += PL_THREADS) slab[i] = wsl[i] + wsl[n + i];
-}
-
-// ---- per-row pieces ------------------------------------------------------------
-__device__ __forceinline__ void load_win(const float *row, float (&win)[WIN]) {
-  const f32x4 *r4 = (const f32x4 *)row;
-#pragma unroll
-  for (int j = 0; j < 12; j++) {
-    const f32x4 q = r4[j];
-    win[4 * j] = q[0];
-    win[4 * j + 1] = q[1];
-    win[4 * j + 2] = q[2];
-    win[4 * j + 3] = q[3];
-  }
-  win[48] = row[48];
-}
-
+// ---- per-row pieces (the shared ones: lnw_learn.inc) ---------------------------------
 // a channel's own statistics (mean, biased variance), summed in double: a
 // constant map (a dead ship's zero row: every conv1 output is the bias) then has
 // mean = the value and variance 0 exactly, as in exact arithmetic. With float
@@ -207,16 +145,6 @@ __device__ __forceinline__ void inst_stats(const float (&v)[N], float &mean, flo
   var = (float)(q / (double)N);
 }
 
-// first maximum of a window's four values in row-major order (strict >)
-__device__ __forceinline__ float first_max4(float a, float b, float c, float d, int &sel) {
-  float best = a;
-  sel = 0;
-  if (b > best) { best = b; sel = 1; }
-  if (c > best) { best = c; sel = 2; }
-  if (d > best) { best = d; sel = 3; }
-  return best;
-}
-
 // conv1 -> BN (the row's statistics) -> ReLU -> 2x2 pool: the pooled maps into
 // pc; st: null, or the row's statistics out (mean at [c * sstride], unbiased
 // variance at [(13 + c) * sstride])
@@ -233,17 +161,7 @@ __device__ __forceinline__ void fwd_p1(const float *P, const float (&win)[WIN], 
       st[c * sstride] = m;
       st[(13 + c) * sstride] = var * (49.0f / 48.0f);
     }
-    const float inv = 1.0f / sqrtf(var + BN_EPS), g = P[B1W + c], b = P[B1B + c];
-#pragma unroll
-    for (int i = 0; i < 49; i++) v[i] = fmaxf((v[i] - m) * inv * g + b, 0.f);
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-      for (int j = 0; j < 3; j++) {
-        const int r0 = 2 * i, c0 = 2 * j;
-        pc[(c * 9 + i * 3 + j) * PL_THREADS] =
-            fmaxf(fmaxf(v[r0 * 7 + c0], v[r0 * 7 + c0 + 1]), fmaxf(v[(r0 + 1) * 7 + c0], v[(r0 + 1) * 7 + c0 + 1]));
-      }
+    bn_relu_pool1(v, c, m, 1.0f / sqrtf(var + BN_EPS), P[B1W + c], P[B1B + c], pc);
   }
 }
 
@@ -253,12 +171,12 @@ __device__ __forceinline__ const float *obs_row(const lnw_ppolearn_args &a, long
 }
 
 // ---- features: conv head, LayerNorm, the row's statistics ---------------------------
-__global__ __launch_bounds__(PL_THREADS) void pl_features_kernel(lnw_ppolearn_args a, Ws w, int n_in) {
-  float *P = pl_lds;  // [CONV_PARAMS + 2 n_in, padded to 712]
-  float *pc = pl_lds + 712 + threadIdx.x;
-  for (int i = threadIdx.x; i < CONV_PARAMS + 2 * n_in; i += PL_THREADS) P[i] = a.actor_params[i];
+__global__ __launch_bounds__(LEARN_THREADS) void pl_features_kernel(lnw_ppolearn_args a, Ws w, int n_in) {
+  float *P = pl_lds;  // [FEAT_LDS]: CONV_PARAMS + 2 n_in
+  float *pc = pl_lds + FEAT_LDS + threadIdx.x;
+  for (int i = threadIdx.x; i < CONV_PARAMS + 2 * n_in; i += LEARN_THREADS) P[i] = a.actor_params[i];
   __syncthreads();
-  const long long r = (long long)blockIdx.x * PL_THREADS + threadIdx.x;
+  const long long r = (long long)blockIdx.x * LEARN_THREADS + threadIdx.x;
   if (r >= a.rows) return;
   const float *row = obs_row(a, r);
   const long long rp = w.rows_pad;
@@ -276,7 +194,7 @@ __global__ __launch_bounds__(PL_THREADS) void pl_features_kernel(lnw_ppolearn_ar
 #pragma unroll 1
     for (int c0 = 0; c0 < 8; c0 += 4) {
       float v2[4][9];
-      conv2_raw(P, pc, PL_THREADS, c0, v2);
+      conv2_raw(P, pc, LEARN_THREADS, c0, v2);
 #pragma unroll
       for (int co = 0; co < 4; co++) {
         const int c = c0 + co;
@@ -589,9 +507,9 @@ __global__ __launch_bounds__(ADV_THREADS) void pl_advantage_kernel(lnw_ppolearn_
 }
 
 // ---- actor loss and the head gradients, per row ------------------------------------------------
-__global__ __launch_bounds__(PL_THREADS) void pl_actorloss_kernel(lnw_ppolearn_args a, Ws w) {
-  double *dsl = (double *)pl_lds;  // [PL_WAVES]
-  const long long r = (long long)blockIdx.x * PL_THREADS + threadIdx.x;
+__global__ __launch_bounds__(LEARN_THREADS) void pl_actorloss_kernel(lnw_ppolearn_args a, Ws w) {
+  double *dsl = (double *)pl_lds;  // [LEARN_WAVES]
+  const long long r = (long long)blockIdx.x * LEARN_THREADS + threadIdx.x;
   const bool valid = r < a.rows;
   const long long rc = valid ? r : a.rows - 1;
   const float adv = w.col[WS_ADV * w.rows_pad + rc];
@@ -645,8 +563,8 @@ __global__ __launch_bounds__(WAVE) void pl_actorloss_sum_kernel(lnw_ppolearn_arg
 
 // ---- LayerNorm backward ---------------------------------------------------------------------
 // per row: the gradient of the head's 12 outputs (the rest of the row is data)
-__global__ __launch_bounds__(PL_THREADS) void pl_lnbwd_kernel(lnw_ppolearn_args a, Ws w, int n_in) {
-  const long long r = (long long)blockIdx.x * PL_THREADS + threadIdx.x;
+__global__ __launch_bounds__(LEARN_THREADS) void pl_lnbwd_kernel(lnw_ppolearn_args a, Ws w, int n_in) {
+  const long long r = (long long)blockIdx.x * LEARN_THREADS + threadIdx.x;
   if (r >= a.rows) return;
   const float *lw = a.actor_params + CONV_PARAMS;
   const float *dx = w.x0 + r * LDW, *xh = w.xh + r * LDW;
@@ -681,13 +599,13 @@ __global__ __launch_bounds__(WAVE) void pl_lnwgrad_kernel(lnw_ppolearn_args a, W
 }
 
 // ---- conv2 pass: convhead, pool 2, BN2, conv2, pool 1 ------------------------------------------
-__global__ __launch_bounds__(PL_THREADS) void pl_conv2grad_kernel(lnw_ppolearn_args a, Ws w) {
-  float *P = pl_lds;  // [CONV_PARAMS, padded to 592]
-  float *parkA = P + 592, *parkB = parkA + PARK;
-  float *wsl = parkB + PARK;  // [PL_WAVES][S4_N]
-  for (int i = threadIdx.x; i < CONV_PARAMS; i += PL_THREADS) P[i] = a.actor_params[i];
+__global__ __launch_bounds__(LEARN_THREADS) void pl_conv2grad_kernel(lnw_ppolearn_args a, Ws w) {
+  float *P = pl_lds;  // [CONV_LDS]
+  float *parkA = P + CONV_LDS, *parkB = parkA + PARK;
+  float *wsl = parkB + PARK;  // [LEARN_WAVES][S4_N_TAIL]
+  for (int i = threadIdx.x; i < CONV_PARAMS; i += LEARN_THREADS) P[i] = a.actor_params[i];
   __syncthreads();
-  const long long r = (long long)blockIdx.x * PL_THREADS + threadIdx.x;
+  const long long r = (long long)blockIdx.x * LEARN_THREADS + threadIdx.x;
   const bool valid = r < a.rows;
   const long long rc = valid ? r : a.rows - 1;
   const float vf = valid ? 1.f : 0.f;
@@ -697,19 +615,19 @@ __global__ __launch_bounds__(PL_THREADS) void pl_conv2grad_kernel(lnw_ppolearn_a
   load_win(obs_row(a, rc), win);
   fwd_p1(P, win, pA, nullptr, 0);
 #pragma unroll
-  for (int k = 0; k < 45; k++) pB[k * PL_THREADS] = 0.f;
+  for (int k = 0; k < 45; k++) pB[k * LEARN_THREADS] = 0.f;
   float dh[12];
 #pragma unroll
   for (int k = 0; k < 12; k++) {
     dh[k] = valid ? w.col[(WS_DH + k) * rp + rc] : 0.f;
-    accum(wsl, S4_N, S4_HB + k, dh[k]);
+    accum(wsl, S4_N_TAIL, S4_HB + k, dh[k]);
   }
   {
 #pragma clang fp contract(fast)
 #pragma unroll 1
     for (int c0 = 0; c0 < 8; c0 += 4) {
       float dz[4][9];
-      conv2_raw(P, pA, PL_THREADS, c0, dz);
+      conv2_raw(P, pA, LEARN_THREADS, c0, dz);
       // BN2 backward with the row's own statistics: dz = g inv (dy - mean(dy) - xh mean(dy xh)),
       // dy the pooled output's gradient at the pool's position
 #pragma unroll
@@ -729,11 +647,11 @@ __global__ __launch_bounds__(PL_THREADS) void pl_conv2grad_kernel(lnw_ppolearn_a
 #pragma unroll
         for (int k = 0; k < 12; k++) {
           d += dh[k] * P[HW + k * 8 + c];
-          accum(wsl, S4_N, S4_HW + k * 8 + c, dh[k] * f);
+          accum(wsl, S4_N_TAIL, S4_HW + k * 8 + c, dh[k] * f);
         }
         const float gy = f > 0.f ? d : 0.f;
-        accum(wsl, S4_N, S4_B2W + c, gy * xs);
-        accum(wsl, S4_N, S4_B2B + c, gy);
+        accum(wsl, S4_N_TAIL, S4_B2W + c, gy * xs);
+        accum(wsl, S4_N_TAIL, S4_B2B + c, gy);
         // (the two means and their subtraction in double: with the row's own
         // statistics 1 / sqrt(var + eps) reaches 316 on a constant map, and the
         // rounding of mean(dy) itself, the same in all 9 terms, would add up
@@ -748,40 +666,9 @@ __global__ __launch_bounds__(PL_THREADS) void pl_conv2grad_kernel(lnw_ppolearn_a
           dz[co][q] = gi * (float)(((double)dy - m0) - (double)xh * m1);
           sb += (double)dz[co][q];
         }
-        accum(wsl, S4_N, S4_C2B + c, (float)sb);
+        accum(wsl, S4_N_TAIL, S4_C2B + c, (float)sb);
       }
-#pragma unroll 1
-      for (int ci = 0; ci < 5; ci++) {
-        float pin[9], dp[9];
-#pragma unroll
-        for (int k = 0; k < 9; k++) {
-          pin[k] = pA[(ci * 9 + k) * PL_THREADS];
-          dp[k] = 0.f;
-        }
-#pragma unroll
-        for (int co = 0; co < 4; co++) {
-          const float *wt = P + C2W + ((c0 + co) * 5 + ci) * 9;
-#pragma unroll
-          for (int ki = 0; ki < 3; ki++)
-#pragma unroll
-            for (int kj = 0; kj < 3; kj++) {
-              float s = 0.f;
-#pragma unroll
-              for (int i = 0; i < 3; i++)
-#pragma unroll
-                for (int j = 0; j < 3; j++) {
-                  const int ii = i + ki - 1, jj = j + kj - 1;
-                  if (ii >= 0 && ii < 3 && jj >= 0 && jj < 3) {
-                    s += dz[co][i * 3 + j] * pin[ii * 3 + jj];
-                    dp[ii * 3 + jj] += wt[ki * 3 + kj] * dz[co][i * 3 + j];
-                  }
-                }
-              accum(wsl, S4_N, S4_C2W + ((c0 + co) * 5 + ci) * 9 + ki * 3 + kj, s);
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 9; k++) pB[(ci * 9 + k) * PL_THREADS] += dp[k];
-      }
+      conv2_bwd(P, pA, pB, c0, dz, wsl, S4_N_TAIL);
     }
   }
   // through pool 1 and the ReLU: conv1 again, channel by channel
@@ -793,47 +680,33 @@ __global__ __launch_bounds__(PL_THREADS) void pl_conv2grad_kernel(lnw_ppolearn_a
       conv1_ch(P, win, c, v);
       float m, var;
       inst_stats<49>(v, m, var);
-      const float inv = 1.0f / sqrtf(var + BN_EPS), g = P[B1W + c], b = P[B1B + c];
+      const float inv = 1.0f / sqrtf(var + BN_EPS);
 #pragma unroll
       for (int i = 0; i < 49; i++) v[i] = (v[i] - m) * inv;
-      float t1 = 0.f, t2 = 0.f;
-      unsigned pos1 = 0;
-#pragma unroll
-      for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-          const int q = i * 3 + j, p0 = 2 * i * 7 + 2 * j;
-          const float h0 = v[p0], h1 = v[p0 + 1], h2 = v[p0 + 7], h3 = v[p0 + 8];
-          int sel;
-          const float best = first_max4(fmaxf(h0 * g + b, 0.f), fmaxf(h1 * g + b, 0.f), fmaxf(h2 * g + b, 0.f),
-                                        fmaxf(h3 * g + b, 0.f), sel);
-          const float xh = sel == 0 ? h0 : sel == 1 ? h1 : sel == 2 ? h2 : h3;
-          const float gy = best > 0.f ? pB[(c * 9 + q) * PL_THREADS] : 0.f;
-          t1 += gy;
-          t2 += gy * xh;
-          pos1 |= (unsigned)sel << (2 * q);
-          if (valid) w.col[(WS_GY1 + c * 9 + q) * rp + r] = gy;
-        }
+      float t1, t2;
+      unsigned pos1;
+      pool1_bwd(v, P[B1W + c], P[B1B + c], pB + c * 9 * LEARN_THREADS, valid,
+                w.col + (WS_GY1 + c * 9) * rp + r, rp, pos1, t1, t2);
       if (valid) {
         ((int *)w.col)[(WS_POS1 + c) * rp + r] = (int)pos1;
         // BN1's backward sums over the row's own 49 values
         w.col[(WS_T + c) * rp + r] = t1;
         w.col[(WS_T + 5 + c) * rp + r] = t2;
       }
-      accum(wsl, S4_N, S4_B1W + c, t2);
-      accum(wsl, S4_N, S4_B1B + c, t1);
+      accum(wsl, S4_N_TAIL, S4_B1W + c, t2);
+      accum(wsl, S4_N_TAIL, S4_B1B + c, t1);
     }
   }
-  flush(wsl, S4_N, w.fslab + (long long)blockIdx.x * CONV_SLABW);
+  flush(wsl, S4_N_TAIL, w.fslab + (long long)blockIdx.x * CONV_SLABW);
 }
 
 // ---- conv1 pass: BN1 backward, conv1 gradients ---------------------------------------------
-__global__ __launch_bounds__(PL_THREADS) void pl_conv1grad_kernel(lnw_ppolearn_args a, Ws w) {
-  float *P = pl_lds;       // [CONV_PARAMS, padded to 592]
-  float *wsl = P + 592;    // [PL_WAVES][S5_N]
-  for (int i = threadIdx.x; i < CONV_PARAMS; i += PL_THREADS) P[i] = a.actor_params[i];
+__global__ __launch_bounds__(LEARN_THREADS) void pl_conv1grad_kernel(lnw_ppolearn_args a, Ws w) {
+  float *P = pl_lds;           // [CONV_LDS]
+  float *wsl = P + CONV_LDS;   // [LEARN_WAVES][S5_N]
+  for (int i = threadIdx.x; i < CONV_PARAMS; i += LEARN_THREADS) P[i] = a.actor_params[i];
   __syncthreads();
-  const long long r = (long long)blockIdx.x * PL_THREADS + threadIdx.x;
+  const long long r = (long long)blockIdx.x * LEARN_THREADS + threadIdx.x;
   const bool valid = r < a.rows;
   const long long rc = valid ? r : a.rows - 1;
   const float vf = valid ? 1.f : 0.f;
@@ -877,20 +750,7 @@ __global__ __launch_bounds__(PL_THREADS) void pl_conv1grad_kernel(lnw_ppolearn_a
         sb += (double)v[i];
       }
       accum(wsl, S5_N, S5_C1B + c, (float)sb);
-#pragma unroll
-      for (int ki = 0; ki < 3; ki++)
-#pragma unroll
-        for (int kj = 0; kj < 3; kj++) {
-          float s = 0.f;
-#pragma unroll
-          for (int i = 0; i < 7; i++)
-#pragma unroll
-            for (int j = 0; j < 7; j++) {
-              const int ii = i + ki - 1, jj = j + kj - 1;
-              if (ii >= 0 && ii < 7 && jj >= 0 && jj < 7) s += v[i * 7 + j] * win[ii * 7 + jj];
-            }
-          accum(wsl, S5_N, S5_C1W + c * 9 + ki * 3 + kj, s);
-        }
+      conv1_wgrad(v, win, c, wsl);
     }
   }
   flush(wsl, S5_N, w.fslab + (long long)blockIdx.x * CONV_SLABW);
@@ -905,29 +765,9 @@ __global__ __launch_bounds__(256) void pl_reduce_conv_kernel(lnw_ppolearn_args a
   for (int b = lane; b < w.nblk; b += WAVE) s += (double)w.fslab[(long long)b * CONV_SLABW + i];
   s = wave_sum_d(s);
   if (lane != 0) return;
-  int dst;
-  if (kind == RED_CONV2) {
-    dst = i < S4_C2B   ? C2W + i
-          : i < S4_B1W ? C2B + (i - S4_C2B)
-          : i < S4_B1B ? B1W + (i - S4_B1W)
-          : i < S4_HW  ? B1B + (i - S4_B1B)
-          : i < S4_HB  ? HW + (i - S4_HW)
-          : i < S4_B2W ? HB + (i - S4_HB)
-          : i < S4_B2B ? B2W + (i - S4_B2W)
-                       : B2B + (i - S4_B2B);
-  } else {
-    dst = i < S5_C1B ? C1W + i : C1B + (i - S5_C1B);
-  }
-  a.actor_grad[dst] = (float)s;
+  a.actor_grad[conv_grad_slot(kind, i, true)] = (float)s;
   // the running statistics' and logstd's slots of the gradient vector are zero
-  if (kind == RED_CONV1 && i < 5) {
-    a.actor_grad[B1M + i] = 0.f;
-    a.actor_grad[B1V + i] = 0.f;
-  }
-  if (kind == RED_CONV1 && i < 8) {
-    a.actor_grad[B2M + i] = 0.f;
-    a.actor_grad[B2V + i] = 0.f;
-  }
+  zero_running_slots(a.actor_grad, kind, i);
   if (kind == RED_CONV1 && i == 0) a.actor_grad[logstd] = 0.f;
 }
 
@@ -989,8 +829,8 @@ struct Plan {
 
 bool make_plan(long long rows, int n, int D, Plan &p) {
   if (rows < 1 || rows + 256 >= (1ll << 31) || n < 1 || n > 16 || !obs_width_ok(D, true)) return false;
-  p.nblk = (int)((rows + PL_THREADS - 1) / PL_THREADS);
-  p.rows_pad = (long long)p.nblk * PL_THREADS;
+  p.nblk = (int)((rows + LEARN_THREADS - 1) / LEARN_THREADS);
+  p.rows_pad = (long long)p.nblk * LEARN_THREADS;
   p.nchunks = (int)((rows + 255) / 256);
   if (p.nchunks > 512) p.nchunks = 512;
   p.chunk_rows = (int)((((rows + p.nchunks - 1) / p.nchunks) + 3) & ~3ll);
@@ -1110,7 +950,7 @@ int lnw_ppo_grad(const lnw_ppolearn_args *args, void *stream) {
   float *V = w.col + WS_V * p.rows_pad, *DV = w.col + WS_DV * p.rows_pad;
 
   // ---- forward
-  pl_features_kernel<<<nb, PL_THREADS, (712 + PARK) * f4, st>>>(a, w, n_in);
+  pl_features_kernel<<<nb, LEARN_THREADS, (FEAT_LDS + PARK) * f4, st>>>(a, w, n_in);
   const Lin a1 = lin(w.x0, LDW, AP + ao.w1, AP + ao.b1, n_in, FC1, w.h1, FC1, R, 1);
   const Lin a2 = lin(w.h1, FC1, AP + ao.w2, AP + ao.b2, FC1, FC2, w.h2, FC2, R, 1);
   const Lin a3 = lin(w.h2, FC2, AP + ao.w3, AP + ao.b3, FC2, FC3, w.h3, FC3, R, 1);
@@ -1132,7 +972,7 @@ int lnw_ppo_grad(const lnw_ppolearn_args *args, void *stream) {
   // ---- advantage, losses, the outputs' gradients
   pl_advantage_kernel<<<1, ADV_THREADS, 2 * ADV_THREADS * sizeof(double), st>>>(a, w, as_decimal(a.gamma),
                                                                               as_decimal(a.lambda_));
-  pl_actorloss_kernel<<<nb, PL_THREADS, PL_WAVES * sizeof(double), st>>>(a, w);
+  pl_actorloss_kernel<<<nb, LEARN_THREADS, LEARN_WAVES * sizeof(double), st>>>(a, w);
   pl_actorloss_sum_kernel<<<1, WAVE, 0, st>>>(a, w);
   // ---- critic backward (each layer's output buffer holds its gradient; dX goes over the input)
   Lin g4 = c4;
@@ -1158,10 +998,10 @@ int lnw_ppo_grad(const lnw_ppolearn_args *args, void *stream) {
                                                                   a.actor_grad, ao.lnw, 0);
   pl_reduce_lin_kernel<<<(unsigned)((n_in + 3) / 4), 256, 0, st>>>(w.fslab + LDW, p.slabw, p.nchunks, n_in, n_in,
                                                                   n_in, a.actor_grad, ao.lnb, 0);
-  pl_lnbwd_kernel<<<nb, PL_THREADS, 0, st>>>(a, w, n_in);
-  pl_conv2grad_kernel<<<nb, PL_THREADS, (size_t)(592 + 2 * PARK + PL_WAVES * S4_N) * f4, st>>>(a, w);
-  pl_reduce_conv_kernel<<<(S4_N + 3) / 4, 256, 0, st>>>(a, w, RED_CONV2, S4_N, ao.logstd);
-  pl_conv1grad_kernel<<<nb, PL_THREADS, (size_t)(592 + PL_WAVES * S5_N) * f4, st>>>(a, w);
+  pl_lnbwd_kernel<<<nb, LEARN_THREADS, 0, st>>>(a, w, n_in);
+  pl_conv2grad_kernel<<<nb, LEARN_THREADS, (size_t)(CONV_LDS + 2 * PARK + LEARN_WAVES * S4_N_TAIL) * f4, st>>>(a, w);
+  pl_reduce_conv_kernel<<<(S4_N_TAIL + 3) / 4, 256, 0, st>>>(a, w, RED_CONV2, S4_N_TAIL, ao.logstd);
+  pl_conv1grad_kernel<<<nb, LEARN_THREADS, (size_t)(CONV_LDS + LEARN_WAVES * S5_N) * f4, st>>>(a, w);
   pl_reduce_conv_kernel<<<(S5_N + 3) / 4, 256, 0, st>>>(a, w, RED_CONV1, S5_N, ao.logstd);
   if (!a.freeze_running) pl_running_kernel<<<26, 256, 4 * sizeof(double), st>>>(a, w);
   return hipGetLastError() == hipSuccess ? 0 : LNW_EDEVICE;
@@ -1170,17 +1010,15 @@ int lnw_ppo_grad(const lnw_ppolearn_args *args, void *stream) {
 int lnw_ppo_clip_adam(float *params, const float *grad, float *m, float *v, int64_t count, int64_t *step_dev,
                       float lr, float beta1, float beta2, float eps, float max_norm, float *scale_norm,
                       void *stream) {
-  if (!params || !grad || !m || !v || !step_dev || !scale_norm || count < 0) return LNW_EINVAL;
-  if (!(lr >= 0.f) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(eps >= 0.f) ||
-      !(max_norm > 0.f))
+  if (!adam_args_ok(params, grad, m, v, count, step_dev, lr, beta1, beta2, eps) || !scale_norm || !(max_norm > 0.f))
     return LNW_EINVAL;
   if (count == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
+  const AdamHyper h = adam_hyper(lr, beta1, beta2, eps);
   pl_norm_kernel<<<1, ADV_THREADS, ADV_THREADS * sizeof(double), st>>>(grad, count, max_norm, scale_norm);
   pl_adam_kernel<<<(unsigned)((count + 255) / 256), 256, 0, st>>>(params, grad, m, v, count,
-                                                                  (const long long *)step_dev, as_decimal(lr),
-                                                                  as_decimal(beta1), as_decimal(beta2),
-                                                                  as_decimal(eps), scale_norm);
+                                                                  (const long long *)step_dev, h.lr, h.beta1,
+                                                                  h.beta2, h.eps, scale_norm);
   pl_advance_kernel<<<1, 1, 0, st>>>((long long *)step_dev);
   return hipGetLastError() == hipSuccess ? 0 : LNW_EDEVICE;
 }

@@ -44,25 +44,19 @@ namespace {
 
 using namespace lnw;
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 #include "lnw_convhead.inc"
+#include "lnw_learn.inc"
 #include "lnw_qhead.inc"
 #include "lnw_adam.inc"
 
-constexpr int QL_THREADS = 128;  // rows per workgroup
-constexpr int QL_WAVES = QL_THREADS / WAVE;
-// LDS copy of the conv head's parameters: the packed 578, with the statistics in
-// use in the M / V slots, then 1 / sqrt(var + eps) of the 5 + 8 channels
-constexpr int I1 = CONV_PARAMS, I2 = CONV_PARAMS + 5, CONV_LDS = 592;
-constexpr int PARK = 45 * QL_THREADS;  // pooled conv1 maps, one column per thread
+// in the LDS copy of the conv head (CONV_LDS floats): the statistics in use in
+// the M / V slots, 1 / sqrt(var + eps) of the 5 + 8 channels behind the packed 578
+constexpr int I1 = CONV_PARAMS, I2 = CONV_PARAMS + 5;
 
-// slab layouts (floats per workgroup) of the three gradient passes
+// slab layouts (floats per workgroup) of the forward pass (the conv passes': lnw_learn.inc)
 constexpr int S3_HW = 0, S3_HB = 96, S3_B2W = 108, S3_B2B = 116, S3_LOSS = 124, S3_N = 125;
-constexpr int S4_C2W = 0, S4_C2B = 360, S4_B1W = 368, S4_B1B = 373, S4_N = 378;
-constexpr int S5_C1W = 0, S5_C1B = 45, S5_N = 50;
 constexpr int SLAB_MIN = 384;
-enum { RED_FWD = 0, RED_HEAD = 1, RED_CONV2 = 2, RED_CONV1 = 3 };
+enum { RED_FWD = 0, RED_HEAD = 1 };  // (then RED_CONV2, RED_CONV1: lnw_learn.inc)
 
 // per-row workspace fields, each [rows_pad]
 constexpr int WS_H = 0, WS_DS = 12, WS_GY2 = 15, WS_GY1 = 23, WS_OIDX = 68, WS_POS2 = 71, WS_POS1 = 72, WS_FIELDS = 77;
@@ -79,57 +73,13 @@ struct Ws {
   int slabw, nblk;
 };
 
-// ---- reductions ------------------------------------------------------------
-__device__ __forceinline__ float dpp_add(float v, const int ctrl_sel) {
-  // (ctrl_sel is a compile-time constant at every call)
-  int x = __builtin_bit_cast(int, v), y;
-  switch (ctrl_sel) {
-    case 0: y = __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xf, 0xf, false); break;   // quad_perm [1,0,3,2]
-    case 1: y = __builtin_amdgcn_update_dpp(0, x, 0x4E, 0xf, 0xf, false); break;   // quad_perm [2,3,0,1]
-    case 2: y = __builtin_amdgcn_update_dpp(0, x, 0x141, 0xf, 0xf, false); break;  // row_half_mirror
-    default: y = __builtin_amdgcn_update_dpp(0, x, 0x140, 0xf, 0xf, false); break; // row_mirror
-  }
-  return v + __builtin_bit_cast(float, y);
-}
-
-// sum over the wave's 64 lanes in a fixed order (all lanes active), wave-uniform
-__device__ __forceinline__ float wave_sum(float v) {
-  v = dpp_add(v, 0);
-  v = dpp_add(v, 1);
-  v = dpp_add(v, 2);
-  v = dpp_add(v, 3);  // every lane: the sum of its row of 16
-  const int x = __builtin_bit_cast(int, v);
-  const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(x, 0));
-  const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(x, 16));
-  const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(x, 32));
-  const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(x, 48));
-  return (r0 + r1) + (r2 + r3);
-}
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-// the workgroup's sum of v into slot idx of its LDS staging [QL_WAVES][n]
-__device__ __forceinline__ void accum(float *wsl, int n, int idx, float v) {
-  const float s = wave_sum(v);
-  if ((threadIdx.x & (WAVE - 1)) == 0) wsl[(threadIdx.x / WAVE) * n + idx] = s;
-}
-
-__device__ __forceinline__ void flush(const float *wsl, int n, float *slab) {
-  __syncthreads();
-  for (int i = threadIdx.x; i < n; i += QL_THREADS) slab[i] = wsl[i] + wsl[n + i];
-}
-
 // ---- staging -----------------------------------------------------------------
 // P <- the packed conv head; with batch statistics, mean and biased variance from
 // the summed moments (s1: conv1 [sum 5, sumsq 5] over n1 values; s2: conv2, or
 // null) into the M / V slots; 1 / sqrt(var + eps) behind.
 __device__ __forceinline__ void stage_conv(float *P, const float *params, const double *s1, double n1,
                                            const double *s2, double n2, bool batch) {
-  for (int i = threadIdx.x; i < CONV_PARAMS; i += QL_THREADS) P[i] = params[i];
+  for (int i = threadIdx.x; i < CONV_PARAMS; i += LEARN_THREADS) P[i] = params[i];
   __syncthreads();
   const int t = threadIdx.x;
   if (t < 13) {
@@ -151,48 +101,14 @@ __device__ __forceinline__ void stage_conv(float *P, const float *params, const 
   __syncthreads();
 }
 
-__device__ __forceinline__ void load_win(const float *row, float (&win)[WIN]) {
-  const f32x4 *r4 = (const f32x4 *)row;
-#pragma unroll
-  for (int j = 0; j < 12; j++) {
-    const f32x4 q = r4[j];
-    win[4 * j] = q[0];
-    win[4 * j + 1] = q[1];
-    win[4 * j + 2] = q[2];
-    win[4 * j + 3] = q[3];
-  }
-  win[48] = row[48];
-}
-
 // ---- forward pieces (conv1_ch, conv2_raw: lnw_convhead.inc) -----------------------
-// first maximum of a window's four values in row-major order (strict >)
-__device__ __forceinline__ float first_max4(float a, float b, float c, float d, int &sel) {
-  float best = a;
-  sel = 0;
-  if (b > best) { best = b; sel = 1; }
-  if (c > best) { best = c; sel = 2; }
-  if (d > best) { best = d; sel = 3; }
-  return best;
-}
-
 // conv1 -> BN (statistics in P) -> ReLU -> 2x2 pool: the pooled maps into pc
 __device__ __forceinline__ void fwd_p1(const float *P, const float (&win)[WIN], float *pc) {
-#pragma clang fp contract(fast)
 #pragma unroll 1
   for (int c = 0; c < 5; c++) {
     float v[49];
     conv1_ch(P, win, c, v);
-    const float m = P[B1M + c], inv = P[I1 + c], g = P[B1W + c], b = P[B1B + c];
-#pragma unroll
-    for (int i = 0; i < 49; i++) v[i] = fmaxf((v[i] - m) * inv * g + b, 0.f);
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-      for (int j = 0; j < 3; j++) {
-        const int r0 = 2 * i, c0 = 2 * j;
-        pc[(c * 9 + i * 3 + j) * QL_THREADS] =
-            fmaxf(fmaxf(v[r0 * 7 + c0], v[r0 * 7 + c0 + 1]), fmaxf(v[(r0 + 1) * 7 + c0], v[(r0 + 1) * 7 + c0 + 1]));
-      }
+    bn_relu_pool1(v, c, P[B1M + c], P[I1 + c], P[B1W + c], P[B1B + c], pc);
   }
 }
 
@@ -212,15 +128,15 @@ __device__ __forceinline__ float head_max(const float *Wl, const float *bl, cons
 }
 
 // ---- pass 1: conv1 moments of both nets -----------------------------------------
-__global__ __launch_bounds__(QL_THREADS) void ql_moments1_kernel(lnw_qlearn_args a, Ws w) {
+__global__ __launch_bounds__(LEARN_THREADS) void ql_moments1_kernel(lnw_qlearn_args a, Ws w) {
   float *Pp = ql_lds, *Pt = ql_lds + CONV_LDS;
-  double *dsl = (double *)(ql_lds + 2 * CONV_LDS);  // [QL_WAVES][20]
-  for (int i = threadIdx.x; i < CONV_PARAMS; i += QL_THREADS) {
+  double *dsl = (double *)(ql_lds + 2 * CONV_LDS);  // [LEARN_WAVES][20]
+  for (int i = threadIdx.x; i < CONV_PARAMS; i += LEARN_THREADS) {
     Pp[i] = a.policy_params[i];
     Pt[i] = a.target_params[i];
   }
   __syncthreads();
-  const long long r = (long long)blockIdx.x * QL_THREADS + threadIdx.x;
+  const long long r = (long long)blockIdx.x * LEARN_THREADS + threadIdx.x;
   const bool valid = r < a.rows;
   const long long rc = valid ? r : a.rows - 1;
 #pragma unroll 1
@@ -252,14 +168,14 @@ __global__ __launch_bounds__(QL_THREADS) void ql_moments1_kernel(lnw_qlearn_args
 }
 
 // ---- pass 2: conv2 moments of both nets -------------------------------------------
-__global__ __launch_bounds__(QL_THREADS) void ql_moments2_kernel(lnw_qlearn_args a, Ws w) {
+__global__ __launch_bounds__(LEARN_THREADS) void ql_moments2_kernel(lnw_qlearn_args a, Ws w) {
   float *Pp = ql_lds, *Pt = ql_lds + CONV_LDS;
   float *pc = ql_lds + 2 * CONV_LDS + threadIdx.x;
-  double *dsl = (double *)(ql_lds + 2 * CONV_LDS + PARK);  // [QL_WAVES][32]
+  double *dsl = (double *)(ql_lds + 2 * CONV_LDS + PARK);  // [LEARN_WAVES][32]
   const double n1 = 49.0 * (double)a.rows;
   stage_conv(Pp, a.policy_params, w.stat1, n1, nullptr, 0.0, a.policy_bn_running == 0);
   stage_conv(Pt, a.target_params, w.stat1 + 10, n1, nullptr, 0.0, true);
-  const long long r = (long long)blockIdx.x * QL_THREADS + threadIdx.x;
+  const long long r = (long long)blockIdx.x * LEARN_THREADS + threadIdx.x;
   const bool valid = r < a.rows;
   const long long rc = valid ? r : a.rows - 1;
 #pragma unroll 1
@@ -273,7 +189,7 @@ __global__ __launch_bounds__(QL_THREADS) void ql_moments2_kernel(lnw_qlearn_args
 #pragma unroll 1
     for (int c0 = 0; c0 < 8; c0 += 4) {
       float v2[4][9];
-      conv2_raw(P, pc, QL_THREADS, c0, v2);
+      conv2_raw(P, pc, LEARN_THREADS, c0, v2);
 #pragma unroll
       for (int co = 0; co < 4; co++) {
         double s = 0.0, q = 0.0;
@@ -308,19 +224,19 @@ __global__ __launch_bounds__(WAVE) void ql_reduce_d_kernel(const double *slab, i
 
 // ---- pass 3: both forwards, loss, head-side gradients --------------------------------
 template <int NI>
-__global__ __launch_bounds__(QL_THREADS) void ql_forward_kernel(lnw_qlearn_args a, Ws w, int n_in) {
+__global__ __launch_bounds__(LEARN_THREADS) void ql_forward_kernel(lnw_qlearn_args a, Ws w, int n_in) {
   float *Pp = ql_lds, *Pt = Pp + CONV_LDS;
   float *Wp = Pt + CONV_LDS, *Wt = Wp + Q_OUT * NI;
   float *bp = Wt + Q_OUT * NI, *bt = bp + BIAS_PAD;
   float *park = bt + BIAS_PAD;
-  float *wsl = park + PARK;  // [QL_WAVES][S3_N]
+  float *wsl = park + PARK;  // [LEARN_WAVES][S3_N]
   const double n1 = 49.0 * (double)a.rows, n2 = 9.0 * (double)a.rows;
   stage_conv(Pp, a.policy_params, w.stat1, n1, w.stat2, n2, a.policy_bn_running == 0);
   stage_conv(Pt, a.target_params, w.stat1 + 10, n1, w.stat2 + 16, n2, true);
-  stage_heads<NI>(Wp, bp, a.policy_params, n_in, QL_THREADS);
-  stage_heads<NI>(Wt, bt, a.target_params, n_in, QL_THREADS);
+  stage_heads<NI>(Wp, bp, a.policy_params, n_in, LEARN_THREADS);
+  stage_heads<NI>(Wt, bt, a.target_params, n_in, LEARN_THREADS);
   __syncthreads();
-  const long long r = (long long)blockIdx.x * QL_THREADS + threadIdx.x;
+  const long long r = (long long)blockIdx.x * LEARN_THREADS + threadIdx.x;
   const bool valid = r < a.rows;
   const long long rc = valid ? r : a.rows - 1;
   float *pc = park + threadIdx.x;
@@ -331,7 +247,7 @@ __global__ __launch_bounds__(QL_THREADS) void ql_forward_kernel(lnw_qlearn_args 
     const float *row = a.next_state + rc * a.D;
     float h[12];
     // (the batch statistics are in the M / V slots: the running-mode path of the shared head)
-    conv_head_row(Pt, row, pc, QL_THREADS, true, h);
+    conv_head_row(Pt, row, pc, LEARN_THREADS, true, h);
 #pragma unroll
     for (int k = 0; k < 12; k++) x[k] = h[k];
     load_tail<NI>(row, n_in, x);
@@ -363,7 +279,7 @@ __global__ __launch_bounds__(QL_THREADS) void ql_forward_kernel(lnw_qlearn_args 
 #pragma unroll
     for (int c0 = 0; c0 < 8; c0 += 4) {
       float v2[4][9];
-      conv2_raw(Pp, pc, QL_THREADS, c0, v2);
+      conv2_raw(Pp, pc, LEARN_THREADS, c0, v2);
 #pragma unroll
       for (int co = 0; co < 4; co++) {
         const int c = c0 + co;
@@ -441,7 +357,7 @@ __global__ __launch_bounds__(QL_THREADS) void ql_forward_kernel(lnw_qlearn_args 
   flush(wsl, S3_N, w.fslab + (long long)blockIdx.x * w.slabw);
 }
 
-// ---- head gradients: one wave per (chunk of QL_THREADS rows, output) ----------------
+// ---- head gradients: one wave per (chunk of LEARN_THREADS rows, output) ----------------
 __global__ __launch_bounds__(WAVE) void ql_headgrad_kernel(lnw_qlearn_args a, Ws w, int n_in) {
   const int o = blockIdx.y, hd = o < 2 ? 0 : (o < 7 ? 1 : 2);
   const int lane = threadIdx.x;
@@ -450,8 +366,8 @@ __global__ __launch_bounds__(WAVE) void ql_headgrad_kernel(lnw_qlearn_args a, Ws
   const long long rp = w.rows_pad;
   float acc = 0.f, bsum = 0.f;
 #pragma unroll 1
-  for (int half = 0; half < QL_THREADS / WAVE; half++) {
-    const long long r0 = (long long)blockIdx.x * QL_THREADS + half * WAVE;
+  for (int half = 0; half < LEARN_THREADS / WAVE; half++) {
+    const long long r0 = (long long)blockIdx.x * LEARN_THREADS + half * WAVE;
     const long long r = r0 + lane;
     const bool match = r < a.rows && ir[(WS_OIDX + hd) * rp + r] == o;
     const float d = match ? fr[(WS_DS + hd) * rp + r] : 0.f;
@@ -476,11 +392,11 @@ __global__ __launch_bounds__(WAVE) void ql_headgrad_kernel(lnw_qlearn_args a, Ws
 }
 
 // ---- pass 4: BN2 backward, conv2 gradients, BN1's backward sums ----------------------
-__global__ __launch_bounds__(QL_THREADS) void ql_conv2grad_kernel(lnw_qlearn_args a, Ws w) {
+__global__ __launch_bounds__(LEARN_THREADS) void ql_conv2grad_kernel(lnw_qlearn_args a, Ws w) {
   float *P = ql_lds;
   float *S = P + CONV_LDS;  // [16] BN2's backward means: sum(dy) / n, sum(dy xh) / n
   float *parkA = S + 16, *parkB = parkA + PARK;
-  float *wsl = parkB + PARK;  // [QL_WAVES][S4_N]
+  float *wsl = parkB + PARK;  // [LEARN_WAVES][S4_N]
   const double n1 = 49.0 * (double)a.rows, n2 = 9.0 * (double)a.rows;
   const bool batch = a.policy_bn_running == 0;
   if (threadIdx.x < 8) {
@@ -488,7 +404,7 @@ __global__ __launch_bounds__(QL_THREADS) void ql_conv2grad_kernel(lnw_qlearn_arg
     S[8 + threadIdx.x] = batch ? (float)((double)a.grad[B2W + threadIdx.x] / n2) : 0.f;
   }
   stage_conv(P, a.policy_params, w.stat1, n1, w.stat2, n2, batch);
-  const long long r = (long long)blockIdx.x * QL_THREADS + threadIdx.x;
+  const long long r = (long long)blockIdx.x * LEARN_THREADS + threadIdx.x;
   const bool valid = r < a.rows;
   const long long rc = valid ? r : a.rows - 1;
   const float vf = valid ? 1.f : 0.f;
@@ -500,14 +416,14 @@ __global__ __launch_bounds__(QL_THREADS) void ql_conv2grad_kernel(lnw_qlearn_arg
   load_win(a.state + rc * a.D, win);
   fwd_p1(P, win, pA);
 #pragma unroll
-  for (int k = 0; k < 45; k++) pB[k * QL_THREADS] = 0.f;
+  for (int k = 0; k < 45; k++) pB[k * LEARN_THREADS] = 0.f;
   const unsigned pos2 = (unsigned)ir[WS_POS2 * rp + rc];
   {
 #pragma clang fp contract(fast)
 #pragma unroll 1
     for (int c0 = 0; c0 < 8; c0 += 4) {
       float dz[4][9];
-      conv2_raw(P, pA, QL_THREADS, c0, dz);
+      conv2_raw(P, pA, LEARN_THREADS, c0, dz);
       // BN2 backward: dz = g inv (dy - mean(dy) - xh mean(dy xh)); dy is gy2 at the pool's position
 #pragma unroll
       for (int co = 0; co < 4; co++) {
@@ -525,38 +441,7 @@ __global__ __launch_bounds__(QL_THREADS) void ql_conv2grad_kernel(lnw_qlearn_arg
         }
         accum(wsl, S4_N, S4_C2B + c, sb);
       }
-#pragma unroll 1
-      for (int ci = 0; ci < 5; ci++) {
-        float pin[9], dp[9];
-#pragma unroll
-        for (int k = 0; k < 9; k++) {
-          pin[k] = pA[(ci * 9 + k) * QL_THREADS];
-          dp[k] = 0.f;
-        }
-#pragma unroll
-        for (int co = 0; co < 4; co++) {
-          const float *wt = P + C2W + ((c0 + co) * 5 + ci) * 9;
-#pragma unroll
-          for (int ki = 0; ki < 3; ki++)
-#pragma unroll
-            for (int kj = 0; kj < 3; kj++) {
-              float s = 0.f;
-#pragma unroll
-              for (int i = 0; i < 3; i++)
-#pragma unroll
-                for (int j = 0; j < 3; j++) {
-                  const int ii = i + ki - 1, jj = j + kj - 1;
-                  if (ii >= 0 && ii < 3 && jj >= 0 && jj < 3) {
-                    s += dz[co][i * 3 + j] * pin[ii * 3 + jj];
-                    dp[ii * 3 + jj] += wt[ki * 3 + kj] * dz[co][i * 3 + j];
-                  }
-                }
-              accum(wsl, S4_N, S4_C2W + ((c0 + co) * 5 + ci) * 9 + ki * 3 + kj, s);
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 9; k++) pB[(ci * 9 + k) * QL_THREADS] += dp[k];
-      }
+      conv2_bwd(P, pA, pB, c0, dz, wsl, S4_N);
     }
   }
   // through pool 1 and the ReLU: conv1 again, channel by channel
@@ -566,27 +451,13 @@ __global__ __launch_bounds__(QL_THREADS) void ql_conv2grad_kernel(lnw_qlearn_arg
     for (int c = 0; c < 5; c++) {
       float v[49];
       conv1_ch(P, win, c, v);
-      const float m = P[B1M + c], inv = P[I1 + c], g = P[B1W + c], b = P[B1B + c];
+      const float m = P[B1M + c], inv = P[I1 + c];
 #pragma unroll
       for (int i = 0; i < 49; i++) v[i] = (v[i] - m) * inv;
-      float t1 = 0.f, t2 = 0.f;
-      unsigned pos1 = 0;
-#pragma unroll
-      for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-          const int q = i * 3 + j, p0 = 2 * i * 7 + 2 * j;
-          const float h0 = v[p0], h1 = v[p0 + 1], h2 = v[p0 + 7], h3 = v[p0 + 8];
-          int sel;
-          const float best = first_max4(fmaxf(h0 * g + b, 0.f), fmaxf(h1 * g + b, 0.f), fmaxf(h2 * g + b, 0.f),
-                                        fmaxf(h3 * g + b, 0.f), sel);
-          const float xh = sel == 0 ? h0 : sel == 1 ? h1 : sel == 2 ? h2 : h3;
-          const float gy = best > 0.f ? pB[(c * 9 + q) * QL_THREADS] : 0.f;
-          t1 += gy;
-          t2 += gy * xh;
-          pos1 |= (unsigned)sel << (2 * q);
-          if (valid) w.row[(WS_GY1 + c * 9 + q) * rp + r] = gy;
-        }
+      float t1, t2;
+      unsigned pos1;
+      pool1_bwd(v, P[B1W + c], P[B1B + c], pB + c * 9 * LEARN_THREADS, valid, w.row + (WS_GY1 + c * 9) * rp + r, rp,
+                pos1, t1, t2);
       if (valid) ((int *)w.row)[(WS_POS1 + c) * rp + r] = (int)pos1;
       accum(wsl, S4_N, S4_B1W + c, t2);
       accum(wsl, S4_N, S4_B1B + c, t1);
@@ -596,10 +467,10 @@ __global__ __launch_bounds__(QL_THREADS) void ql_conv2grad_kernel(lnw_qlearn_arg
 }
 
 // ---- pass 5: BN1 backward, conv1 gradients --------------------------------------------
-__global__ __launch_bounds__(QL_THREADS) void ql_conv1grad_kernel(lnw_qlearn_args a, Ws w) {
+__global__ __launch_bounds__(LEARN_THREADS) void ql_conv1grad_kernel(lnw_qlearn_args a, Ws w) {
   float *P = ql_lds;
   float *T = P + CONV_LDS;  // [10] BN1's backward means
-  float *wsl = T + 16;      // [QL_WAVES][S5_N]
+  float *wsl = T + 16;      // [LEARN_WAVES][S5_N]
   const double n1 = 49.0 * (double)a.rows;
   const bool batch = a.policy_bn_running == 0;
   if (threadIdx.x < 5) {
@@ -607,7 +478,7 @@ __global__ __launch_bounds__(QL_THREADS) void ql_conv1grad_kernel(lnw_qlearn_arg
     T[5 + threadIdx.x] = batch ? (float)((double)a.grad[B1W + threadIdx.x] / n1) : 0.f;
   }
   stage_conv(P, a.policy_params, w.stat1, n1, nullptr, 0.0, batch);
-  const long long r = (long long)blockIdx.x * QL_THREADS + threadIdx.x;
+  const long long r = (long long)blockIdx.x * LEARN_THREADS + threadIdx.x;
   const bool valid = r < a.rows;
   const long long rc = valid ? r : a.rows - 1;
   const float vf = valid ? 1.f : 0.f;
@@ -646,20 +517,7 @@ __global__ __launch_bounds__(QL_THREADS) void ql_conv1grad_kernel(lnw_qlearn_arg
         sb += v[i];
       }
       accum(wsl, S5_N, S5_C1B + c, sb);
-#pragma unroll
-      for (int ki = 0; ki < 3; ki++)
-#pragma unroll
-        for (int kj = 0; kj < 3; kj++) {
-          float s = 0.f;
-#pragma unroll
-          for (int i = 0; i < 7; i++)
-#pragma unroll
-            for (int j = 0; j < 7; j++) {
-              const int ii = i + ki - 1, jj = j + kj - 1;
-              if (ii >= 0 && ii < 7 && jj >= 0 && jj < 7) s += v[i * 7 + j] * win[ii * 7 + jj];
-            }
-          accum(wsl, S5_N, S5_C1W + c * 9 + ki * 3 + kj, s);
-        }
+      conv1_wgrad(v, win, c, wsl);
     }
   }
   flush(wsl, S5_N, w.fslab + (long long)blockIdx.x * w.slabw);
@@ -685,21 +543,11 @@ __global__ __launch_bounds__(256) void ql_reduce_kernel(lnw_qlearn_args a, Ws w,
     dst = i < S3_HB ? HW + i : i < S3_B2W ? HB + (i - S3_HB) : i < S3_B2B ? B2W + (i - S3_B2W) : B2B + (i - S3_B2B);
   } else if (kind == RED_HEAD) {
     dst = CONV_PARAMS + i;
-  } else if (kind == RED_CONV2) {
-    dst = i < S4_C2B ? C2W + i : i < S4_B1W ? C2B + (i - S4_C2B) : i < S4_B1B ? B1W + (i - S4_B1W) : B1B + (i - S4_B1B);
   } else {
-    dst = i < S5_C1B ? C1W + i : C1B + (i - S5_C1B);
+    dst = conv_grad_slot(kind, i, false);
   }
   a.grad[dst] = (float)s;
-  // the running statistics' slots of the gradient vector are zero
-  if (kind == RED_CONV1 && i < 5) {
-    a.grad[B1M + i] = 0.f;
-    a.grad[B1V + i] = 0.f;
-  }
-  if (kind == RED_CONV1 && i < 8) {
-    a.grad[B2M + i] = 0.f;
-    a.grad[B2V + i] = 0.f;
-  }
+  zero_running_slots(a.grad, kind, i);
 }
 
 // ---- batch statistics out, running statistics (momentum 0.1, unbiased variance) ----------
@@ -750,9 +598,9 @@ int slab_width(int n_in) {
 extern "C" {
 
 int64_t lnw_qlearn_workspace_bytes(int64_t rows, int32_t D) {
-  if (rows < 1 || rows + QL_THREADS >= (1ll << 31) || !obs_width_ok(D, true)) return 0;
-  const int64_t nblk = (rows + QL_THREADS - 1) / QL_THREADS;
-  return 512 + nblk * 32 * 8 + nblk * slab_width(D - WIN + 12) * 4 + (int64_t)WS_FIELDS * nblk * QL_THREADS * 4;
+  if (rows < 1 || rows + LEARN_THREADS >= (1ll << 31) || !obs_width_ok(D, true)) return 0;
+  const int64_t nblk = (rows + LEARN_THREADS - 1) / LEARN_THREADS;
+  return 512 + nblk * 32 * 8 + nblk * slab_width(D - WIN + 12) * 4 + (int64_t)WS_FIELDS * nblk * LEARN_THREADS * 4;
 }
 
 int lnw_qnet_grad(const lnw_qlearn_args *args, void *stream) {
@@ -765,13 +613,13 @@ int lnw_qnet_grad(const lnw_qlearn_args *args, void *stream) {
   // 16-B aligned rows for the vector loads
   if (((uintptr_t)a.state & 15) || ((uintptr_t)a.next_state & 15) || ((uintptr_t)a.workspace & 15)) return LNW_EINVAL;
   if (!obs_width_ok(a.D, true)) return LNW_EUNSUPPORTED;
-  if (a.rows + QL_THREADS >= (1ll << 31)) return LNW_EUNSUPPORTED;
+  if (a.rows + LEARN_THREADS >= (1ll << 31)) return LNW_EUNSUPPORTED;
   if (a.workspace_bytes < lnw_qlearn_workspace_bytes(a.rows, a.D)) return LNW_EINVAL;
   const int n_in = a.D - WIN + 12;
   Ws w;
-  w.nblk = (int)((a.rows + QL_THREADS - 1) / QL_THREADS);
+  w.nblk = (int)((a.rows + LEARN_THREADS - 1) / LEARN_THREADS);
   w.slabw = slab_width(n_in);
-  w.rows_pad = (long long)w.nblk * QL_THREADS;
+  w.rows_pad = (long long)w.nblk * LEARN_THREADS;
   char *base = (char *)a.workspace;
   w.stat1 = (double *)base;
   w.stat2 = w.stat1 + 20;
@@ -781,23 +629,23 @@ int lnw_qnet_grad(const lnw_qlearn_args *args, void *stream) {
   hipStream_t st = (hipStream_t)stream;
   const unsigned nb = (unsigned)w.nblk;
   const size_t f4 = sizeof(float);
-  ql_moments1_kernel<<<nb, QL_THREADS, (2 * CONV_LDS) * f4 + QL_WAVES * 20 * 8, st>>>(a, w);
+  ql_moments1_kernel<<<nb, LEARN_THREADS, (2 * CONV_LDS) * f4 + LEARN_WAVES * 20 * 8, st>>>(a, w);
   ql_reduce_d_kernel<<<20, WAVE, 0, st>>>(w.dslab, w.nblk, w.stat1);
-  ql_moments2_kernel<<<nb, QL_THREADS, (2 * CONV_LDS + PARK) * f4 + QL_WAVES * 32 * 8, st>>>(a, w);
+  ql_moments2_kernel<<<nb, LEARN_THREADS, (2 * CONV_LDS + PARK) * f4 + LEARN_WAVES * 32 * 8, st>>>(a, w);
   ql_reduce_d_kernel<<<32, WAVE, 0, st>>>(w.dslab, w.nblk, w.stat2);
   const int NI = n_in <= 32 ? 32 : MAX_IN;
-  const size_t lds3 = (size_t)(2 * CONV_LDS + 2 * Q_OUT * NI + 2 * BIAS_PAD + PARK + QL_WAVES * S3_N) * f4;
+  const size_t lds3 = (size_t)(2 * CONV_LDS + 2 * Q_OUT * NI + 2 * BIAS_PAD + PARK + LEARN_WAVES * S3_N) * f4;
   if (NI == 32)
-    ql_forward_kernel<32><<<nb, QL_THREADS, lds3, st>>>(a, w, n_in);
+    ql_forward_kernel<32><<<nb, LEARN_THREADS, lds3, st>>>(a, w, n_in);
   else
-    ql_forward_kernel<MAX_IN><<<nb, QL_THREADS, lds3, st>>>(a, w, n_in);
+    ql_forward_kernel<MAX_IN><<<nb, LEARN_THREADS, lds3, st>>>(a, w, n_in);
   ql_reduce_kernel<<<(S3_N + 3) / 4, 256, 0, st>>>(a, w, RED_FWD, S3_N, n_in);
   ql_headgrad_kernel<<<dim3(nb, Q_OUT), WAVE, 0, st>>>(a, w, n_in);
   const int nhead = Q_OUT * n_in + Q_OUT;
   ql_reduce_kernel<<<(nhead + 3) / 4, 256, 0, st>>>(a, w, RED_HEAD, nhead, n_in);
-  ql_conv2grad_kernel<<<nb, QL_THREADS, (size_t)(CONV_LDS + 16 + 2 * PARK + QL_WAVES * S4_N) * f4, st>>>(a, w);
+  ql_conv2grad_kernel<<<nb, LEARN_THREADS, (size_t)(CONV_LDS + 16 + 2 * PARK + LEARN_WAVES * S4_N) * f4, st>>>(a, w);
   ql_reduce_kernel<<<(S4_N + 3) / 4, 256, 0, st>>>(a, w, RED_CONV2, S4_N, n_in);
-  ql_conv1grad_kernel<<<nb, QL_THREADS, (size_t)(CONV_LDS + 16 + QL_WAVES * S5_N) * f4, st>>>(a, w);
+  ql_conv1grad_kernel<<<nb, LEARN_THREADS, (size_t)(CONV_LDS + 16 + LEARN_WAVES * S5_N) * f4, st>>>(a, w);
   ql_reduce_kernel<<<(S5_N + 3) / 4, 256, 0, st>>>(a, w, RED_CONV1, S5_N, n_in);
   ql_stats_kernel<<<1, WAVE, 0, st>>>(a, w);
   return hipGetLastError() == hipSuccess ? 0 : LNW_EDEVICE;
@@ -805,15 +653,13 @@ int lnw_qnet_grad(const lnw_qlearn_args *args, void *stream) {
 
 int lnw_qnet_adam(float *params, const float *grad, float *m, float *v, int64_t count, int64_t *step_dev, float lr,
                   float beta1, float beta2, float eps, float clamp, void *stream) {
-  if (!params || !grad || !m || !v || !step_dev || count < 0) return LNW_EINVAL;
-  if (!(lr >= 0.f) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(eps >= 0.f))
-    return LNW_EINVAL;
+  if (!adam_args_ok(params, grad, m, v, count, step_dev, lr, beta1, beta2, eps)) return LNW_EINVAL;
   if (count == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
+  const AdamHyper h = adam_hyper(lr, beta1, beta2, eps);
   ql_adam_kernel<<<(unsigned)((count + 255) / 256), 256, 0, st>>>(params, grad, m, v, count,
-                                                                  (const long long *)step_dev, as_decimal(lr),
-                                                                  as_decimal(beta1), as_decimal(beta2),
-                                                                  as_decimal(eps), clamp);
+                                                                  (const long long *)step_dev, h.lr, h.beta1,
+                                                                  h.beta2, h.eps, clamp);
   ql_advance_kernel<<<1, 1, 0, st>>>((long long *)step_dev);
   return hipGetLastError() == hipSuccess ? 0 : LNW_EDEVICE;
 }

@@ -33,7 +33,6 @@ namespace {
 
 using namespace lnw;
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 #include "lnw_convhead.inc"
