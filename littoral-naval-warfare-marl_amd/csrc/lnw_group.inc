@@ -587,41 +587,6 @@ __device__ __forceinline__ void get_obs_group(Ctx &X, int me, int sub, const GSi
   GPROF_ADD(X, 7, tq);
 }
 
-// Tail float t (after the terrain window) of agent k's observation row, the
-// same value build_row writes: self x/G, y/G, radar, missiles/(4|8); every other
-// own ship (ships that acted before k in their new state, the others in their
-// old one; sunk: zeros); len(target_list), is-landing-ship, ducting/2; zeros
-// to the row end (combatant.py:163-233, landingship.py:167-239).
-__device__ __forceinline__ float row_tail(const KParams &P, const Cols &c, const double *duct_col,
-                                          int el, int k, int tk, uint32_t p, int own0, int ns,
-                                          int kl, int t) {
-  const double G = (double)P.G;
-  if (t < 4) {
-    if (t == 0) return (float)((double)pos_x(p) / G);
-    if (t == 1) return (float)((double)pos_y(p) / G);
-    if (t == 2) return (float)c.radar_cur[k * PAD + el];
-    return (float)c.miss_cur[k * PADB + el] * (tk == T_SMALL ? 0.25f : 0.125f);
-  }
-  t -= 4;
-  if (t < 4 * (ns - 1)) {
-    const int s = t >> 2, comp = t & 3;
-    const int il = s < kl ? s : s + 1, i = own0 + il;
-    if (!c.alive0[i * PADB + el]) return 0.0f;
-    const bool nw = il < kl;
-    const uint32_t q = nw ? c.pos_cur[i * PAD + el] : c.pos_old[i * PAD + el];
-    if (comp == 0) return (float)((double)pos_x(q) / G);
-    if (comp == 1) return (float)((double)pos_y(q) / G);
-    if (comp == 2) return (float)(nw ? c.radar_cur[i * PAD + el] : c.radar_old[i * PAD + el]);
-    const int m = nw ? c.miss_cur[i * PADB + el] : c.miss_old[i * PADB + el];
-    return (float)m * (c.type[i * PADB + el] == T_SMALL ? 0.25f : 0.125f);
-  }
-  t -= 4 * (ns - 1);
-  if (t == 0) return (float)c.tcnt[k * PAD + el];
-  if (t == 1) return tk == T_LS ? 1.0f : 0.0f;
-  if (t == 2) return (float)(duct_col[el] / 2.0);
-  return 0.0f;
-}
-
 // Phase O of the group kernel: the env's observation rows, one side's block
 // [ns rows][D] contiguous in the output; lane sub builds and stores float4
 // chunks sub, sub + GL, ... (window floats straight from the per-cell record).

@@ -1885,10 +1885,58 @@ __device__ inline Rng make_rng(const KParams &P, const KState &S, int env) {
 // wave then copies each side's block ([envs][n][D], contiguous in the output)
 // out with consecutive lanes on consecutive floats (256-B coalesced stores).
 // ---------------------------------------------------------------------------
-// Builds one observation row of D floats into an LDS row (stride D+1: odd, so
-// a ds_write_b32 across lanes is conflict-free). The terrain window comes from
-// the per-cell window table (Combatant 49 floats padded to 52, LandingShip 25
-// padded to 28): 13 / 7 independent float4 loads issued together.
+// The content of an observation row of ship k (get_obs, combatant.py:163-233,
+// landingship.py:167-239):
+//   window | tail | zeros to the row end
+// window: the ship's terrain window record (Combatant 7x7 = 49 floats,
+//   LandingShip and medium Combatant 5x5 = 25).
+// tail, 4 ns + 3 floats: own x/G, y/G, radar, missiles/(4|8); the same four
+//   of every other own ship in fleet order (ships that acted before k this
+//   step in their new, *_cur, state, the others in their old, *_old, one;
+//   sunk: zeros); len(target_list), is-landing-ship, ducting/2.
+// A sunk ship's whole row is zero. row_tail is the element-wise definition for
+// runtime team sizes (group_rows); build_row below it is the same tail
+// unrolled over one row. The compile-time forms (row_build_t, emit_rows_t,
+// emit_rows_al4_t) spell the tail out again: DESIGN.md, "The observation
+// row's content", has what sharing it cost them.
+// Float t of the tail of live agent k's row (type tk, cell p, own ship kl of
+// the ns ships from own0), zeros past the tail.
+__device__ __forceinline__ float row_tail(const KParams &P, const Cols &c, const double *duct_col,
+                                          int el, int k, int tk, uint32_t p, int own0, int ns,
+                                          int kl, int t) {
+  const double G = (double)P.G;
+  if (t < 4) {
+    if (t == 0) return (float)((double)pos_x(p) / G);
+    if (t == 1) return (float)((double)pos_y(p) / G);
+    if (t == 2) return (float)c.radar_cur[k * PAD + el];
+    return (float)c.miss_cur[k * PADB + el] * (tk == T_SMALL ? 0.25f : 0.125f);
+  }
+  t -= 4;
+  if (t < 4 * (ns - 1)) {
+    const int s = t >> 2, comp = t & 3;
+    const int il = s < kl ? s : s + 1, i = own0 + il;
+    if (!c.alive0[i * PADB + el]) return 0.0f;
+    const bool nw = il < kl;
+    const uint32_t q = nw ? c.pos_cur[i * PAD + el] : c.pos_old[i * PAD + el];
+    if (comp == 0) return (float)((double)pos_x(q) / G);
+    if (comp == 1) return (float)((double)pos_y(q) / G);
+    if (comp == 2) return (float)(nw ? c.radar_cur[i * PAD + el] : c.radar_old[i * PAD + el]);
+    const int m = nw ? c.miss_cur[i * PADB + el] : c.miss_old[i * PADB + el];
+    return (float)m * (c.type[i * PADB + el] == T_SMALL ? 0.25f : 0.125f);
+  }
+  t -= 4 * (ns - 1);
+  if (t == 0) return (float)c.tcnt[k * PAD + el];
+  if (t == 1) return tk == T_LS ? 1.0f : 0.0f;
+  if (t == 2) return (float)(duct_col[el] / 2.0);
+  return 0.0f;
+}
+
+// row_tail's unrolled form: one lane builds a whole row of D floats into an
+// LDS row (stride D+1: odd, so a ds_write_b32 across lanes is conflict-free),
+// x/G from the wave's table (xg) instead of a float64 division per float. The
+// terrain window comes from the per-cell window table (Combatant 49 floats
+// padded to 52, LandingShip 25 padded to 28): 13 / 7 independent float4 loads
+// issued together.
 __device__ __forceinline__ void build_row(const KParams &P, const KState &S, const Cols &c, const double *duct_col,
                           int el, int k, float *row, const float *xg, bool only_observed) {
   const int side = k >= P.nb;
@@ -2029,7 +2077,7 @@ __device__ __forceinline__ void write_obs(const KParams &P, const KState &S, Col
 // how many stores follow the prefetched window loads), and the next pass's
 // window loads are issued before this pass's stores, so waiting for them never
 // drains the stores (vmcnt counts loads and stores together in issue order).
-// One observation row assembled in registers (same content as build_row):
+// One observation row assembled in registers (the content described at row_tail):
 // every LDS read is issued up front without branches, teammate slot s holds
 // own ship s < kl ? s : s + 1 (combatant.py:190-212), and the row leaves as
 // D/4 ds_write_b128. Combatant rows: window[49] | tail; LandingShip rows:
