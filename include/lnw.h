@@ -251,8 +251,14 @@ int lnw_tlist_cap(lnw_handle *h);
  * shape, no reference counterpart). epw = 0 restores the automatic choice made
  * by lnw_load_terrain: 64 (one env per lane) unless E is too small to fill the
  * GPU, then fewer per workgroup. 1 <= epw <= 64 forces it (results do not depend
- * on it; tests use it to cover both launch shapes). Returns the epw in force, or
- * a negative LNW_E* code. */
+ * on it; tests use it to cover both launch shapes). Every value in 1..64 is
+ * supported, powers of two or not (the automatic choice only makes powers of
+ * two); no value in that range is refused, anything else is LNW_EINVAL. The
+ * quiet path's form follows from it: rows written directly by wave 1 up to
+ * 64 / nb envs (4v4: up to 128 / nb in two slabs), staged passes above, the
+ * units kernel at 64 ("The quiet predicate at sensor reach"). The
+ * LNW_EPW_RT environment variable (1..64) overrides the automatic choice the
+ * same way. Returns the epw in force, or a negative LNW_E* code. */
 int lnw_set_epw(lnw_handle *h, int32_t epw);
 
 /* Step-kernel code variant for 2v2 / 3v3 / 4v4 (build-side, no reference
