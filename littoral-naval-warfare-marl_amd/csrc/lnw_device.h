@@ -646,24 +646,54 @@ __device__ inline bool check_path_dev(const Blocked &blocked, bool start_blocked
 // rounds the same way. Returns false otherwise (the caller then takes the
 // double sincos path, about 1 row in 10^4 for uniform rows): the cell is the
 // exact path's for every row either way (CPU check of both paths).
+// SEL: the same verdict and cell with no branch at all, for phase M's
+// interleaved passes (move_stages_f32), where the early returns and the
+// quadrant's chain of ?: (it compiles to branches) would part one pass from the
+// next. A row out of range then goes through the arithmetic as deg = 0,
+// dist = 0, so that every conversion in it stays defined, and comes out
+// uncertain; the quadrant n = k mod 4 (sin = sr, cr, -sr, -cr; cos = cr, -sr,
+// -cr, sr) is one select and one sign bit each: the same floats, bit for bit.
+// nx and ny are then written whatever the verdict.
+template <bool SEL = false>
 __device__ inline bool move_cell_f32_fast(int px, int py, double deg, float dist, int &nx, int &ny) {
-  if (!(fabs(deg) < 1.0e5) || !(fabsf(dist) <= 4.0f)) return false;
+  bool in = true;
+  if constexpr (SEL) {
+    in = fabs(deg) < 1.0e5 && fabsf(dist) <= 4.0f;
+    deg = in ? deg : 0.0;
+    dist = in ? dist : 0.0f;
+  } else {
+    if (!(fabs(deg) < 1.0e5) || !(fabsf(dist) <= 4.0f)) return false;
+  }
   const double k = rint(deg * 6.36619772367581382433e-01);  // 2 / pi
   double rd = fma(-k, 1.57079632673412561417e+00, deg);      // pi/2, first 33 bits: exact
   rd = fma(-k, 6.07710050650619224932e-11, rd);              // the rest of pi/2
   const float r = (float)rd, z = r * r;
   const float sr = r + r * z * (-1.6666667e-1f + z * (8.3333333e-3f + z * (-1.9841270e-4f + z * 2.7557319e-6f)));
   const float cr = 1.0f - 0.5f * z + z * z * (4.1666668e-2f + z * (-1.3888889e-3f + z * 2.4801587e-5f));
-  const int n = (int)k & 3;
-  const float s = n == 0 ? sr : n == 1 ? cr : n == 2 ? -sr : -cr;
-  const float c = n == 0 ? cr : n == 1 ? -sr : n == 2 ? -cr : sr;
-  const float fx = (float)px + c * dist, fy = (float)py + s * dist;
-  if (!(fabsf(fx) < 256.0f && fabsf(fy) < 256.0f)) return false;
-  const float rx = rintf(fx), ry = rintf(fy);
-  if (fabsf(fabsf(fx - rx) - 0.5f) < 4e-5f || fabsf(fabsf(fy - ry) - 0.5f) < 4e-5f) return false;
-  nx = (int)rx;
-  ny = (int)ry;
-  return true;
+  if constexpr (SEL) {
+    const uint32_t n = (uint32_t)(int)k;
+    const bool odd = n & 1u;
+    const float s = __uint_as_float(__float_as_uint(odd ? cr : sr) ^ ((n & 2u) << 30));
+    const float c = __uint_as_float(__float_as_uint(odd ? sr : cr) ^ (((n + 1u) & 2u) << 30));
+    const float fx = (float)px + c * dist, fy = (float)py + s * dist;
+    const float rx = rintf(fx), ry = rintf(fy);
+    nx = (int)rx;  // (|fx| < 2^15 + 4: defined)
+    ny = (int)ry;
+    const bool small = fabsf(fx) < 256.0f && fabsf(fy) < 256.0f;
+    const bool tie = fabsf(fabsf(fx - rx) - 0.5f) < 4e-5f || fabsf(fabsf(fy - ry) - 0.5f) < 4e-5f;
+    return in && small && !tie;
+  } else {
+    const int n = (int)k & 3;
+    const float s = n == 0 ? sr : n == 1 ? cr : n == 2 ? -sr : -cr;
+    const float c = n == 0 ? cr : n == 1 ? -sr : n == 2 ? -cr : sr;
+    const float fx = (float)px + c * dist, fy = (float)py + s * dist;
+    if (!(fabsf(fx) < 256.0f && fabsf(fy) < 256.0f)) return false;
+    const float rx = rintf(fx), ry = rintf(fy);
+    if (fabsf(fabsf(fx - rx) - 0.5f) < 4e-5f || fabsf(fabsf(fy - ry) - 0.5f) < 4e-5f) return false;
+    nx = (int)rx;
+    ny = (int)ry;
+    return true;
+  }
 }
 
 __device__ inline bool move_target_dev(int px, int py, int speed, double a2, double a3, int kind,

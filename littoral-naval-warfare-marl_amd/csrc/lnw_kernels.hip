@@ -2726,6 +2726,125 @@ __device__ __forceinline__ bool move_batch_t(const KParams &P, const KState &S, 
   return pend;
 }
 
+// The preloaded float32 rows with a compile-time pass count NP: move_batch_t's
+// result for every row, computed in stages across the wave's NP pairs instead
+// of pair after pair, so that the passes' LDS and table round trips overlap and
+// no pass waits for the branches of the one before. Every LDS read of the phase
+// comes before its first LDS write; the reads and the targets compile to one
+// stretch without a branch, and the rows the float polynomials cannot certify
+// (and the non-finite ones) go through move_target_dev in one loop behind a
+// wave-uniform branch: one copy of the double sincos, entered about once in 40
+// waves for uniform rows. (DESIGN.md "Headline phase M, interleaved".)
+template <int NP, int MAXP>
+__device__ __forceinline__ bool move_stages_f32(const KParams &P, const KState &S, Cols &c,
+                                                const uint32_t *mask, int env0, int nenv, int A, int p0,
+                                                const f32x4 (&vf)[MAXP]) {
+  static_assert(NP >= 1 && NP <= MAXP && NP <= 8, "one batch of passes");
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int npair = nenv * A;
+  // (a) the columns of every pair
+  int e[NP], a[NP], sx[NP], sy[NP], t[NP];
+  uint32_t p[NP];
+  // per-pair verdicts as bits of a lane's word (bit k: pair k), not as bools: NP
+  // lane masks each would live in scalar registers the kernel has none to spare of
+  uint32_t live = 0;
+#pragma unroll
+  for (int k = 0; k < NP; k++) {
+    const int q = (p0 + k) * WAVE + lane;
+    const int qc = q < npair ? q : 0;  // absent pairs re-read pair 0 (never live)
+    e[k] = qc / A;
+    a[k] = qc - e[k] * A;
+    live |= (q < npair && c.alive0[a[k] * PADB + e[k]] != 0) ? 1u << k : 0u;
+    p[k] = c.pos_old[a[k] * PAD + e[k]];
+    t[k] = c.type[a[k] * PADB + e[k]];
+    sx[k] = pos_x(p[k]);
+    sy[k] = pos_y(p[k]);
+  }
+  // (b) every pair's cell by the float polynomials (continuous_to_discrete as
+  // move_target_dev states it for K_F32), certain or not
+  int nx[NP], ny[NP];
+  uint32_t ok = 0;  // the cell is known
+#pragma unroll
+  for (int k = 0; k < NP; k++) {
+    const float course = (float)(2.0 * PY_PI) * vf[k].z;
+    const float dist = (float)ship_speed(t[k]) * vf[k].w;
+    const double deg = (double)course * RAD2DEG;
+    const bool sure = move_cell_f32_fast<true>(sx[k], sy[k], deg, dist, nx[k], ny[k]);
+    ok |= sure ? 1u << k : 0u;
+  }
+  ok &= live;
+  uint32_t slow = live & ~ok;  // still to be found
+  // the other rows, one per lane and turn
+  if (__any(slow != 0)) {
+#pragma unroll 1
+    do {
+      if (slow) {
+        const int ks = __ffs(slow) - 1;
+        int px = sx[0], py = sy[0], tt = t[0], es = e[0];
+        float a2 = vf[0].z, a3 = vf[0].w;
+#pragma unroll
+        for (int k = 1; k < NP; k++)
+          if (ks == k) { px = sx[k]; py = sy[k]; tt = t[k]; es = e[k]; a2 = vf[k].z; a3 = vf[k].w; }
+        int mx, my;
+        const bool fin = move_target_dev(px, py, ship_speed(tt), a2, a3, K_F32, mx, my);
+        if (!fin) atomicOr(&S.err[env0 + es], (uint32_t)LNW_ERRF_NAN_ROUND);
+#pragma unroll
+        for (int k = 0; k < NP; k++)
+          if (ks == k) { nx[k] = mx; ny[k] = my; }
+        if (fin) ok |= 1u << ks;
+        slow &= slow - 1;
+      }
+    } while (__any(slow != 0));
+  }
+  // (c) can_move_to (combatant.py:482-489): every pair's mask word
+  uint32_t mword[NP];
+  uint32_t ingrid = 0;
+#pragma unroll
+  for (int k = 0; k < NP; k++) {
+    // (& on purpose, here and below: && would put each pair behind its own branches)
+    const bool in = ((ok >> k) & 1u) & ((uint32_t)nx[k] < 100u) & ((uint32_t)ny[k] < 100u);
+    ingrid |= in ? 1u << k : 0u;
+    mword[k] = mask[(in ? nx[k] : 0) * P.W16 + (in ? ny[k] >> 4 : 0)];
+  }
+  // (d) check_path from the move table where the target lies in its window
+  // (move_mode 0): every pair's table word
+  uint32_t cand = 0;
+  int mw[NP];
+  uint32_t w[NP];
+#pragma unroll
+  for (int k = 0; k < NP; k++) {
+    const bool cd = ((ingrid >> k) & 1u) & !((mword[k] >> ((ny[k] & 15) * 2)) & 1u);
+    cand |= cd ? 1u << k : 0u;
+    const int ox = nx[k] - sx[k], oy = ny[k] - sy[k];
+    const bool inwin = cd & (P.move_mode == 0) & ((uint32_t)(ox + R_MV) <= 2u * R_MV) &
+                       ((uint32_t)(oy + R_MV) <= 2u * R_MV);
+    const int bit = inwin ? (ox + R_MV) * MV_W + (oy + R_MV) : 0;
+    mw[k] = inwin ? (int)(((size_t)mv_cls(t[k]) * P.G * P.G + (size_t)sx[k] * P.G + sy[k]) * MV_WORDS +
+                          (bit >> 5)) * 32 + (bit & 31)
+                  : -1;
+    w[k] = S.mvtab[mw[k] >= 0 ? mw[k] >> 5 : 0];
+  }
+  // (e) the phase's LDS writes: the row's first two values for phase S (live
+  // pairs only: a sunk ship's akind byte stays), and the move
+  bool pend = false;
+#pragma unroll
+  for (int k = 0; k < NP; k++) {
+    if ((live >> k) & 1u) {
+      c.act0[a[k] * PAD + e[k]] = vf[k].x;
+      c.act1[a[k] * PAD + e[k]] = vf[k].y;
+      c.akind[a[k] * PADB + e[k]] = (uint8_t)K_F32;
+    }
+    if ((cand >> k) & 1u) {  // (else pos_new stays p: load_state)
+      const uint32_t cell = pack_pos(nx[k], ny[k]);
+      const bool feas = (w[k] >> (mw[k] & 31)) & 1u;
+      // outside the table: left flagged for the A* pass
+      c.pos_new[a[k] * PAD + e[k]] = mw[k] < 0 ? (cell | 0x40000000u) : feas ? (cell | 0x80000000u) : p[k];
+      pend |= mw[k] < 0;
+    }
+  }
+  return pend;
+}
+
 // check_path by A* for the candidates the table did not cover (still flagged
 // 0x40000000 in pos_new): one copy of the search for every action dtype.
 __device__ __forceinline__ void move_astar_pass(const KParams &P, const KState &S, Cols &c,
@@ -2766,10 +2885,14 @@ __device__ __forceinline__ void preload_rows_f32(const void *actions, int env0, 
     v[k] = *(const f32x4 *)((const float *)actions + ((size_t)env0 * A + q) * 4);
   }
 }
-template <int NW, int MAXP>
+// NPC > 0: the wave's pass count where the instantiation fixes it (the units
+// kernel: full 64-env units), which takes the passes interleaved
+// (move_stages_f32); NPC = 0: a runtime count, pass after pass.
+template <int NW, int MAXP, int NPC = 0>
 __device__ __forceinline__ bool move_phase_pre(const KParams &P, const KState &S, Cols &c, const void *actions,
                                                const uint8_t *row_kind, const uint32_t *mask, int env0,
                                                int nenv, int A, int wid, const f32x4 (&v)[MAXP]) {
+  if constexpr (NPC > 0) return move_stages_f32<NPC, MAXP>(P, S, c, mask, env0, nenv, A, wid * NPC, v);
   const int npass = (nenv * A + WAVE - 1) / WAVE;
   const int share = (npass + NW - 1) / NW;
   const int pbeg = wid * share, np = (pbeg + share < npass ? pbeg + share : npass) - pbeg;
@@ -3042,6 +3165,12 @@ __device__ __forceinline__ void step_body(
   // templated team sizes, float32 rows: this wave's action rows in flight across phase L
   // (LNW_DEBUG_SKIP bit 23: loaded in phase M instead)
   constexpr int MAXPRE = 4;  // passes per wave: A <= 8 ships x <= 64 envs over two waves
+  // whole 64-env units: each wave's share of the (NB + NR) * 64 / 64 pair passes
+  // is all there, and known here; 0: a runtime count (move_phase_pre)
+  // (declared here, not in phase M's block: there the 2v2 and 3v3 kernels spilled one
+  // scalar register more than their pins, tests/test_step_args_cpu.py)
+  constexpr int NPC = UN > 1 ? (NB + NR) / 2 : 0;
+  static_assert(UN == 1 || ((NB + NR) % 2 == 0 && NPC <= MAXPRE), "a unit's passes split evenly over its waves");
   const int dt = P.act_dtype;
   const bool pre = ST && NW == 2 && dt == LNW_ACT_F32 && !(P.dbg_skip & 4) && !(P.dbg_skip & 8388608);
   f32x4 vpre[MAXPRE];
@@ -3091,7 +3220,8 @@ __device__ __forceinline__ void step_body(
   bool pend = false;
   if (!(P.dbg_skip & 4)) {
     if (pre)
-      pend = move_phase_pre<NW, MAXPRE>(P, S, c, actions, row_kind, mask, env0, nenv, A, wid, vpre);
+      pend = move_phase_pre<NW, MAXPRE, NPC>(P, S, c, actions, row_kind, mask, env0, UN > 1 ? WAVE : nenv, A,
+                                             wid, vpre);
     else if (dt == LNW_ACT_F32)
       pend = move_phase<LNW_ACT_F32, NW>(P, S, c, actions, row_kind, mask, env0, nenv, A, wid);
     else if (dt == LNW_ACT_F64)
