@@ -680,6 +680,58 @@ int lnw_ppo_clip_adam(float *params, const float *grad, float *m, float *v, int6
                       float lr, float beta1, float beta2, float eps, float max_norm, float *scale_norm,
                       void *stream);
 
+/* ---- MAPPO minibatch draw ------------------------------------------------------
+ * lnw_ppo_sample draws the learner's prioritised minibatch (ppo.py:311-319:
+ * WeightedRandomSampler(|rtg| + 1e-5, batch, replacement=False), i.e.
+ * torch.multinomial without replacement) as a keyed draw: sequential weighted
+ * sampling without replacement is "the `batch` smallest keys e_r / w_r, e_r ~
+ * Exp(1), in ascending order" (Efraimidis-Spirakis), which is what torch does
+ * with its own generator. For local row r, global row g = row_base + r, slot =
+ * *draw_dev:
+ *   w_r = (double)(fabsf(rtg[r]) + 1e-5f)               (the float32 sum first)
+ *   u_r = u53(o[0], o[1]), o = Philox4x32-10 under key `seed` of the counter
+ *         words {lo32(c), hi32(c), LNW_SAMPLE_CTR2, LNW_SAMPLE_CTR3}, c =
+ *         (slot << 40) + g (g < 2^40, slot < 2^24): a domain of its own, no
+ *         draw shared with the rollout's or lnw_fill_uniform_f32's
+ *   k_r = -p_log(1 - u_r) / w_r in double (portable p_log: the same bits on the
+ *         host); a zero key is stored as +0; a row whose rtg is NaN or +-inf
+ *         gets k_r = +inf and is counted in status[0]
+ * The minibatch is the first `batch` rows of the total order (k_r, g): keys
+ * compared as numbers, ties to the lower row. Non-finite rows are therefore
+ * drawn only after every finite row, in row order. The key depends on the global
+ * row alone, so the first `batch` of the union of two shards' (key_out, row_base
+ * + index_out), merged by (key, global row), is what one call over all rows
+ * draws.
+ * The call's last launch gathers actions, log_probs [rows][4], rtg and values[r
+ * / n] of the drawn rows (each where both its input and its output are given)
+ * and, with advance, adds 1 to *draw_dev.
+ * A chain of launches on `stream`: no host synchronisation, no allocation;
+ * integer atomics only in counts and a minimum, which no arrival order changes:
+ * bitwise reproducible, also under graph replay. workspace:
+ * lnw_ppo_sample_workspace_bytes(rows, batch) bytes, 16-B aligned (0 for
+ * unsupported shapes: 1 <= batch <= min(rows, 131072), rows < 2^31). */
+#define LNW_SAMPLE_CTR2 0x13198A2Eu
+#define LNW_SAMPLE_CTR3 0x03707344u
+#define LNW_SAMPLE_MAX_BATCH 131072
+typedef struct lnw_ppo_sample_args {
+  const float *rtg;            /* [rows] */
+  int64_t rows, row_base;      /* 1 <= rows < 2^31; global id of row 0 (0 <= row_base, row_base + rows <= 2^40) */
+  int64_t batch;               /* 1 <= batch <= min(rows, 131072) */
+  uint64_t seed;
+  int64_t *draw_dev;           /* [1] the slot, read on the device (NULL = 0) */
+  int32_t advance;             /* 1: the call's last launch adds 1 to *draw_dev */
+  const float *actions, *log_probs;  /* NULL, or [rows][4] */
+  const float *values;         /* NULL, or [rows / n]: old value of row r is values[r / n] */
+  int32_t n;
+  int64_t *index_out;          /* [batch] local rows in draw order */
+  double  *key_out;            /* NULL, or [batch] */
+  float *actions_out, *log_probs_out, *rtg_out, *old_values_out;  /* NULL, or [batch][4] / [batch] */
+  int64_t *status;             /* NULL, or [1]: rows with a non-finite rtg */
+  void *workspace; int64_t workspace_bytes;
+} lnw_ppo_sample_args;
+int64_t lnw_ppo_sample_workspace_bytes(int64_t rows, int64_t batch);  /* 0: unsupported */
+int lnw_ppo_sample(const lnw_ppo_sample_args *args, void *stream);
+
 /* Host-side constants the kernels use (for tests): hit probability tables
  * 1-(1-p)^n for p in {0.45, 0.63}, n = 0..8, in float64 and float32. */
 int lnw_hit_tables(double *tab64 /* [2][9] */, float *tab32 /* [2][9] */);

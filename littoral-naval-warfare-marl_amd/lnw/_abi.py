@@ -35,7 +35,10 @@ SYMBOLS = [
     "lnw_qlearn_workspace_bytes", "lnw_qnet_grad", "lnw_qnet_adam",
     "lnw_ppolearn_workspace_bytes", "lnw_ppo_grad", "lnw_ppo_clip_adam",
     "lnw_policy_packed_floats", "lnw_actor_perturb", "lnw_policy_act_pop",
+    "lnw_ppo_sample_workspace_bytes", "lnw_ppo_sample",
 ]
+# lnw_ppo_sample's Philox counter words 2 and 3, and its largest batch (include/lnw.h)
+LNW_SAMPLE_CTR2, LNW_SAMPLE_CTR3, LNW_SAMPLE_MAX_BATCH = 0x13198A2E, 0x03707344, 131072
 
 # lnw_step_kernel codes (include/lnw.h LNW_KERNEL_*)
 (KERNEL_NONE, KERNEL_GENERIC, KERNEL_TEAM, KERNEL_TEAM_CONTACT, KERNEL_UNITS, KERNEL_GROUP,
@@ -140,6 +143,15 @@ class PpolearnArgs(C.Structure):  # include/lnw.h: lnw_ppolearn_args
                 ("advantage", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+class PpoSampleArgs(C.Structure):  # include/lnw.h: lnw_ppo_sample_args
+    _fields_ = [("rtg", C.c_void_p), ("rows", C.c_int64), ("row_base", C.c_int64), ("batch", C.c_int64),
+                ("seed", C.c_uint64), ("draw_dev", C.c_void_p), ("advance", C.c_int32),
+                ("actions", C.c_void_p), ("log_probs", C.c_void_p), ("values", C.c_void_p), ("n", C.c_int32),
+                ("index_out", C.c_void_p), ("key_out", C.c_void_p), ("actions_out", C.c_void_p),
+                ("log_probs_out", C.c_void_p), ("rtg_out", C.c_void_p), ("old_values_out", C.c_void_p),
+                ("status", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 class LnwError(RuntimeError):
     pass
 
@@ -204,6 +216,8 @@ def load(path=None):
         "lnw_policy_packed_floats": ([I32], C.c_int64),
         "lnw_actor_perturb": ([C.POINTER(ActorPerturbArgs), P], C.c_int),
         "lnw_policy_act_pop": ([C.POINTER(PolicyArgs), C.POINTER(PolicyPop), P], C.c_int),
+        "lnw_ppo_sample_workspace_bytes": ([I64, I64], C.c_int64),
+        "lnw_ppo_sample": ([C.POINTER(PpoSampleArgs), P], C.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)

@@ -5,8 +5,10 @@ Reference: ppo.py:673-693 (evaluate), ppo.py:695-714 (gae, over the minibatch
 rows as the sequence), ppo.py:716-729 (popart_normalize), ppo.py:342-362 (the
 two losses), ppo.py:371-380 (clip_grad_norm_ and Adam per network),
 ppo.py:311-319 (the prioritised sampler). The kernels are csrc/lnw_ppolearn.hip
-(lnw_ppo_grad, lnw_ppo_clip_adam). learn()'s outer schedule (noise ratio, lr
-halving on victories, epoch count) and red-side training stay with the caller;
+(lnw_ppo_grad, lnw_ppo_clip_adam) and csrc/lnw_pposample.hip (lnw_ppo_sample,
+the keyed minibatch draw behind PPOLearner.minibatch). learn()'s outer schedule
+(noise ratio, lr halving on victories, epoch count) and red-side training stay
+with the caller;
 parameter noise is the rollout's (lnw.rollout.Rollout(param_noise=..., theta=
 learner.theta_actor) acts from this learner's flat vector).
 """
@@ -157,6 +159,49 @@ def running_after(r0, stats, momentum=0.1):
     return (1.0 - momentum) ** B * r0.double() + momentum * (wgt[:, None] * stats.double()).sum(0)
 
 
+def _philox10(c, k0, k1):
+    """Philox4x32-10 on uint64 arrays that hold 32-bit words (lnw_device.h)."""
+    m32 = np.uint64(0xFFFFFFFF)
+    c0, c1, c2, c3 = c
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & m32, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & m32
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & m32, (k1 + np.uint64(0xBB67AE85)) & m32
+    return c0, c1, c2, c3
+
+
+def _p_log(x):
+    """lnw_device.h's portable ln in float64 array operations: the same bits."""
+    m, e = np.frexp(x)
+    low = m < 0.70710678118654752
+    m = np.where(low, m * 2.0, m)
+    e = e - low
+    s = (m - 1.0) / (m + 1.0)
+    z = s * s
+    p = np.full_like(z, 1.0 / 19.0)
+    for d in (17.0, 15.0, 13.0, 11.0, 9.0, 7.0, 5.0, 3.0, 1.0):
+        p = p * z + 1.0 / d
+    return 2.0 * s * p + e.astype(np.float64) * 0.6931471805599453
+
+
+def sample_keys(rtg, seed, slot, row_base=0):
+    """lnw_ppo_sample's keys (include/lnw.h) of a float32 reward-to-go vector on
+    the host: float64 [rows], +inf where rtg is not finite."""
+    from ._abi import LNW_SAMPLE_CTR2, LNW_SAMPLE_CTR3
+    rtg = np.ascontiguousarray(rtg, np.float32).reshape(-1)
+    m32 = np.uint64(0xFFFFFFFF)
+    ctr = np.uint64(int(slot) << 40) + np.uint64(int(row_base)) + np.arange(rtg.shape[0], dtype=np.uint64)
+    seed = int(seed) & (2 ** 64 - 1)
+    o = _philox10((ctr & m32, ctr >> np.uint64(32), np.full_like(ctr, LNW_SAMPLE_CTR2),
+                   np.full_like(ctr, LNW_SAMPLE_CTR3)), np.uint64(seed & 0xFFFFFFFF), np.uint64(seed >> 32))
+    u = ((o[0] >> np.uint64(5)).astype(np.float64) * 67108864.0
+         + (o[1] >> np.uint64(6)).astype(np.float64)) / 9007199254740992.0
+    with np.errstate(all="ignore"):
+        w = (np.abs(rtg) + np.float32(1e-5)).astype(np.float64)
+        key = -_p_log(1.0 - u) / w + 0.0
+    return np.where(np.isfinite(rtg), key, np.inf)
+
+
 class PPOLearner:
     """PPO.learn's minibatch update (ppo.py:321-390) for the blue side on flat
     device vectors: `theta_actor` (actor_slices layout) and `theta_critic`
@@ -177,12 +222,14 @@ class PPOLearner:
     clip_grad_norm_ and torch.optim.Adam on the same flat state, on the host or
     the device — the arm the kernels are tested and timed against.
 
-    batch (what rows() returns): dict(obs [groups, n, D] float32, index [B] int64
-    rows of obs.reshape(-1, D) or None for all rows in order, actions [B, 4],
-    old_log_probs [B, 4], rtg [B], old_values [B])."""
+    batch (what rows() and minibatch() return): dict(obs [groups, n, D] float32,
+    index [B] int64 rows of obs.reshape(-1, D) or None for all rows in order,
+    actions [B, 4], old_log_probs [B, 4], rtg [B], old_values [B]). minibatch()
+    draws the reference's prioritised minibatch on the device (lnw_ppo_sample);
+    sample() is the same distribution through torch.multinomial."""
 
     def __init__(self, actor, critic, lr=1e-4, eps_clip=0.2, entropy_coef=0.2, gamma=0.99, lambda_=0.95,
-                 max_grad_norm=1.0, betas=(0.9, 0.999), eps=1e-8, impl="hip", device=None):
+                 max_grad_norm=1.0, betas=(0.9, 0.999), eps=1e-8, impl="hip", device=None, sample_seed=0):
         if impl not in ("hip", "torch"):
             raise ValueError("impl must be 'hip' or 'torch'")
         if device is None:
@@ -215,6 +262,12 @@ class PPOLearner:
         self.clip = torch.zeros((2, 2), dtype=torch.float32, device=dev)
         self._ws = None
         self._opt = None
+        # minibatch(): the default seed, the draw counter (the slot of the next draw), the last draw's count of
+        # rows with a non-finite rtg, and the output buffers and workspace per (rows, batch)
+        self.sample_seed = int(sample_seed)
+        self.draw = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.sample_status = torch.zeros(1, dtype=torch.int64, device=dev)
+        self._sample_buf = {}
 
     # ---- batches -------------------------------------------------------------------
     def rows(self, out, index=None, rtg=None):
@@ -245,6 +298,85 @@ class PPOLearner:
         rtg = (out["rtg"] if rtg is None else rtg).reshape(-1).to(self.device, torch.float32)
         pr = torch.abs(rtg) + 1e-5
         return torch.multinomial(pr / pr.sum(), int(batch), replacement=False, generator=generator)
+
+    def minibatch(self, out, batch, seed=None, rtg=None, row_base=0, advance=True):
+        """The prioritised minibatch of a Rollout.run() result, drawn and
+        gathered on the device: what rows(out, sample(out, batch)) returns, ready
+        for step() / grad(), plus `key` [batch] float64. The draw is
+        lnw_ppo_sample's (include/lnw.h): the reference sampler's distribution
+        (`batch` distinct rows by priorities |rtg| + 1e-5, in draw order) as a
+        pure function of (seed, draw counter, global row), so it is bitwise
+        reproducible, shards of the rows merge by `key` into the draw over all
+        of them (global row = row_base + index), and a captured graph draws
+        fresh rows at every replay. seed: None for self.sample_seed. The counter
+        self.draw advances by one unless advance is False; self.sample_status
+        counts the rows whose rtg is not finite (drawn last, in row order).
+
+        impl="hip": a chain of launches on the current stream with no host
+        synchronisation, capturable with step() in one torch.cuda.graph; the
+        returned tensors are buffers kept per (rows, batch) that the next call
+        of the same shape overwrites. impl="torch": the same draw from the
+        definition with NumPy on the host (it reads the counter, so it
+        synchronises), the same index bit for bit."""
+        dev = self.device
+        obs = out["obs"]
+        n, D = obs.shape[-2], obs.shape[-1]
+        obs = obs.reshape(-1, n, D).to(dev, torch.float32).contiguous()
+        rtg = (out["rtg"] if rtg is None else rtg).reshape(-1).to(dev, torch.float32).contiguous()
+        acts = out["actions"].reshape(-1, 4).to(dev, torch.float32).contiguous()
+        lps = out["log_probs"].reshape(-1, 4).to(dev, torch.float32).contiguous()
+        vals = out["values"].reshape(-1).to(dev, torch.float32).contiguous()
+        N, B = rtg.shape[0], int(batch)
+        from ._abi import LNW_SAMPLE_MAX_BATCH
+        if not 1 <= B <= min(N, LNW_SAMPLE_MAX_BATCH):
+            raise ValueError(f"batch must be in 1 .. min(rows, {LNW_SAMPLE_MAX_BATCH})")
+        if acts.shape[0] != N or lps.shape[0] != N or vals.shape[0] * n != N:
+            raise ValueError("rtg, actions and log_probs need one row per (env, step, ship), values one per (env, step)")
+        seed = (self.sample_seed if seed is None else int(seed)) & (2 ** 64 - 1)
+        draw = self._sample_hip if self.impl == "hip" else self._sample_torch
+        b = draw(rtg, acts, lps, vals, n, B, seed, int(row_base), bool(advance))
+        return dict(obs=obs, index=b["index"], actions=b["actions"], old_log_probs=b["old_log_probs"], rtg=b["rtg"],
+                    old_values=b["old_values"], key=b["key"])
+
+    def _sample_hip(self, rtg, acts, lps, vals, n, B, seed, row_base, advance):
+        from . import _abi
+        L = _abi.load()
+        dev = self.device
+        N = rtg.shape[0]
+        buf = self._sample_buf.get((N, B))
+        if buf is None:
+            need = L.lnw_ppo_sample_workspace_bytes(N, B)
+            if need <= 0:
+                raise _abi.LnwError(f"lnw_ppo_sample does not support rows={N}, batch={B}")
+            e = lambda *s, dtype=torch.float32: torch.empty(s, dtype=dtype, device=dev)  # noqa: E731
+            buf = dict(index=e(B, dtype=torch.int64), key=e(B, dtype=torch.float64), actions=e(B, 4),
+                       old_log_probs=e(B, 4), rtg=e(B), old_values=e(B), ws=e(need, dtype=torch.uint8))
+            self._sample_buf[(N, B)] = buf
+        a = _abi.PpoSampleArgs()
+        a.rtg, a.rows, a.row_base, a.batch, a.seed = rtg.data_ptr(), N, row_base, B, seed
+        a.draw_dev, a.advance = self.draw.data_ptr(), int(advance)
+        a.actions, a.log_probs, a.values, a.n = acts.data_ptr(), lps.data_ptr(), vals.data_ptr(), n
+        a.index_out, a.key_out = buf["index"].data_ptr(), buf["key"].data_ptr()
+        a.actions_out, a.log_probs_out = buf["actions"].data_ptr(), buf["old_log_probs"].data_ptr()
+        a.rtg_out, a.old_values_out = buf["rtg"].data_ptr(), buf["old_values"].data_ptr()
+        a.status = self.sample_status.data_ptr()
+        a.workspace, a.workspace_bytes = buf["ws"].data_ptr(), buf["ws"].numel()
+        _abi.check(L.lnw_ppo_sample(C.byref(a), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        return buf
+
+    def _sample_torch(self, rtg, acts, lps, vals, n, B, seed, row_base, advance):
+        dev = self.device
+        r = rtg.detach().cpu().numpy()
+        key = sample_keys(r, seed, int(self.draw), row_base)
+        # ascending key, ties to the lower row (keys compare as numbers: sample_keys holds no -0)
+        order = np.lexsort((np.arange(key.shape[0]), key))[:B]
+        index = torch.from_numpy(order.astype(np.int64)).to(dev)
+        self.sample_status.fill_(int((~np.isfinite(r)).sum()))
+        if advance:
+            self.draw += 1
+        return dict(index=index, key=torch.from_numpy(key[order]).to(dev), actions=acts[index].contiguous(),
+                    old_log_probs=lps[index].contiguous(), rtg=rtg[index].contiguous(),
+                    old_values=vals[torch.div(index, n, rounding_mode="floor")].contiguous())
 
     def _batch(self, b):
         dev = self.device
