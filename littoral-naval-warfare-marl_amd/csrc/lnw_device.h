@@ -9,12 +9,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lnw_window.h"
+
 namespace lnw {
 
 constexpr int WAVE = 64;
 // native 4 x f32 vector: arrays of it stay in VGPRs (HIP's union-based float4
 // defeats SROA and lands such arrays in scratch)
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 constexpr int R_MV = 4;           // move-table window: target offsets in [-4, 4]^2
 constexpr int MV_W = 2 * R_MV + 1;
 constexpr int MV_WORDS = 3;       // 81 bits per (class, start cell)
@@ -104,7 +107,7 @@ struct KState {
   const double *atan_deg;  // [LOS_W][LOS_W] degrees(atan2(dy, dx)), host libm (EW bearings)
   const uint8_t *grid;     // [G][G]
   const float *gridf;      // [G][G] grid/255 as float32
-  const float *winf;       // [3][G*G][52] Combatant 7x7 | LandingShip 5x5 | medium Combatant 5x5 observation windows
+  const float *winf;       // [3][G*G][52] Combatant 7x7 | LandingShip 5x5 | medium Combatant 5x5 observation windows; behind them (win_bytes_at) the same windows as [3][G*G][64] raw grid bytes (lnw_window.h)
   float *dummy;            // [WAVE * 4] sink for masked-out stores (keeps store counts static)
   unsigned long long *prof;  // diagnostics (LNW_PROF): [n_wg][16] phase timestamps, else null
   ColdPtr cold;              // the handle's cold block (analytics, work counters, tape RNG, spawn spec, bearing scratch: KCold)
@@ -468,6 +471,28 @@ __host__ __device__ inline int mv_cls(int t) { return t == T_LS ? 1 : (t == T_ME
 // medium Combatant 5x5 (combatant.py:165-181 with speed 2)
 __device__ inline int win_cls(int t) { return mv_cls(t); }
 __device__ inline int win_len(int t) { return t == T_SMALL || t == T_LARGE ? 49 : 25; }
+// One ship's window record as raw grid bytes, in registers: the 64-byte line
+// as four dwordx4 (16 VGPRs, against 49 for the float record), converted to the
+// row's floats only where the row is built. Read by the units kernel's stream
+// (quiet_emit_units_t); the other readers load the 52-float records.
+struct WinRec { u32x4 q[4]; };
+// The byte records stand behind the float records in the same allocation, from
+// the next 64-byte boundary on (in 16-byte units): both readers of a kernel
+// then address one base pointer. A second pointer kept live beside winf cost
+// the units kernel 4 more spilled SGPRs than its budget has.
+__host__ __device__ inline int win_bytes_at(int G) { return (3 * G * G * 13 + 3) & ~3; }
+// rec: the record's index in the table (class * G*G + cell)
+__device__ __forceinline__ void load_win(const float *winf, int G, int rec, WinRec &w) {
+  const u32x4 *r = (const u32x4 *)winf;
+  const int off = win_bytes_at(G) + rec * (LNW_WIN_REC / 16);
+#pragma unroll
+  for (int q = 0; q < 4; q++) w.q[q] = r[off + q];
+}
+// window float j (0 <= j < 64, a compile-time j after unrolling: one
+// v_cvt_f32_ubyte and win_byte_f32's three operations)
+__device__ __forceinline__ float win_f(const WinRec &w, int j) {
+  return win_byte_f32((w.q[j >> 4][(j >> 2) & 3] >> (8 * (j & 3))) & 0xffu);
+}
 // radar / EW range class of a target: small, large-like (large, medium: mast
 // 30, rcs 1), LandingShip (rcs 0.9)
 __device__ inline int rng_cls(int t) { return t == T_SMALL ? 0 : (t == T_LS ? 2 : 1); }

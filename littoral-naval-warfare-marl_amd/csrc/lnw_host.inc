@@ -529,7 +529,8 @@ int lnw_load_terrain(lnw_handle *h, const uint8_t *grid_host, int32_t G) {
   }
   rc |= dalloc(h, &h->d_grid, (size_t)G * G);
   rc |= dalloc(h, &h->d_gridf, (size_t)G * G);
-  rc |= dalloc(h, &h->d_winf, (size_t)3 * G * G * 52);
+  // the float records, then the byte records (win_bytes_at: in 16-byte units)
+  rc |= dalloc(h, &h->d_winf, (size_t)win_bytes_at(G) * 4 + (size_t)LNW_WIN_CLASSES * G * G * LNW_WIN_REC / 4);
   rc |= dalloc(h, &h->d_mask2, (size_t)G * h->W16);
   rc |= dalloc(h, &h->d_mvtab, (size_t)MV_CLASSES * G * G * MV_WORDS);
   rc |= dalloc(h, &h->d_lostab, (size_t)G * G * LOS_CELL_WORDS);
@@ -544,28 +545,20 @@ int lnw_load_terrain(lnw_handle *h, const uint8_t *grid_host, int32_t G) {
     std::vector<float> gf((size_t)G * G);
     for (size_t i = 0; i < gf.size(); i++) gf[i] = (float)((double)grid_host[i] / 255.0);
     HIPCHK(hipMemcpy(h->d_gridf, gf.data(), gf.size() * sizeof(float), hipMemcpyHostToDevice));
-    // per-cell observation windows, one 52-float (13 x float4) record per cell
-    // and class: [0] Combatant 7x7 around the ship (49 floats), [1] LandingShip
-    // 5x5 rows/cols pos-1..pos+3 (25 floats), [2] medium Combatant 5x5 around
-    // the ship (speed 2: combatant.py:165-181); cells outside the hard-coded
-    // 0..99 are 0 (combatant.py:176, landingship.py:183)
-    std::vector<float> wf((size_t)3 * G * G * 52, 0.0f);
-    auto cellv = [&](int x, int y) {
-      return (0 <= x && x < 100 && 0 <= y && y < 100 && x < G && y < G) ? gf[(size_t)x * G + y] : 0.0f;
-    };
-    for (int x = 0; x < G; x++)
-      for (int y = 0; y < G; y++) {
-        float *w7 = &wf[((size_t)x * G + y) * 52];
-        for (int i = 0; i < 7; i++)
-          for (int j = 0; j < 7; j++) w7[i * 7 + j] = cellv(x - 3 + i, y - 3 + j);
-        float *w5 = &wf[((size_t)G * G + (size_t)x * G + y) * 52];
-        for (int i = 0; i < 5; i++)
-          for (int j = 0; j < 5; j++) w5[i * 5 + j] = cellv(x - 1 + i, y - 1 + j);
-        float *wm = &wf[((size_t)2 * G * G + (size_t)x * G + y) * 52];
-        for (int i = 0; i < 5; i++)
-          for (int j = 0; j < 5; j++) wm[i * 5 + j] = cellv(x - 2 + i, y - 2 + j);
-      }
+    // per-cell observation windows, one record per cell and class (lnw_window.h:
+    // [0] Combatant 7x7 around the ship, [1] LandingShip 5x5 rows/cols
+    // pos-1..pos+3, [2] medium Combatant 5x5 around the ship; cells outside the
+    // hard-coded 0..99 are 0): packed once as 64-byte records of raw grid bytes,
+    // which the units kernel's stream converts where it builds a row, and from
+    // those the 52-float (13 x float4) records of the other readers
+    std::vector<uint8_t> wb((size_t)LNW_WIN_CLASSES * G * G * LNW_WIN_REC);
+    win_pack_records(grid_host, G, wb.data());
+    const size_t nrec = wb.size() / LNW_WIN_REC;
+    std::vector<float> wf(nrec * 52, 0.0f);
+    for (size_t r = 0; r < nrec; r++)
+      for (int j = 0; j < 49; j++) wf[r * 52 + j] = (float)((double)wb[r * LNW_WIN_REC + j] / 255.0);
     HIPCHK(hipMemcpy(h->d_winf, wf.data(), wf.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy((char *)h->d_winf + (size_t)win_bytes_at(G) * 16, wb.data(), wb.size(), hipMemcpyHostToDevice));
   }
   KParams &k = h->kp;
   k.G = G;

@@ -55,7 +55,6 @@ __device__ __forceinline__ void st_obs4(f32x4 *base, uint32_t i4, f32x4 v, bool 
     __builtin_nontemporal_store(v, base + i4);
   }
 }
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -2144,6 +2143,72 @@ __device__ inline void row_regs_t(const Cols &c, const double *duct_col, int el,
   row_build_t<NS>(c.pos_cur[k * PAD + el], c.type[k * PADB + el], c.alive0[k * PADB + el],
                   c.radar_cur[k * PAD + el], c.miss_cur[k * PADB + el], c.tcnt[k * PAD + el], duct_col[el], tq,
                   tr, tm, tt, ta, v, w48, row, xg);
+}
+
+// The same row from a byte record (WinRec, lnw_device.h): the window's floats
+// are converted here, in registers (win_f), the rest as row_build_t. The units
+// kernel's stream builds its rows with it; the other readers keep the float
+// records and the functions above, whose code the one-unit kernels' register
+// budgets are pinned on ("Window records as bytes").
+template <int NS>
+__device__ __forceinline__ void row_build_bytes_t(uint32_t p, int tk, int alive, int rad, int mis, uint32_t tcn, double du,
+                                   const uint32_t (&tq)[NS - 1], const int (&tr)[NS - 1], const int (&tm)[NS - 1],
+                                   const int (&tt)[NS - 1], const int (&ta)[NS - 1], const WinRec &v,
+                                         float *row, const float *xg) {
+  constexpr int D = 4 * NS + 52, T = 4 * NS + 3;
+  float t[T];
+  t[0] = xg[pos_x(p)];
+  t[1] = xg[pos_y(p)];
+  t[2] = (float)rad;
+  t[3] = (float)mis * (tk == T_SMALL ? 0.25f : 0.125f);
+#pragma unroll
+  for (int s = 0; s < NS - 1; s++) {
+    const float fx = xg[pos_x(tq[s])], fy = xg[pos_y(tq[s])];
+    const float fm = (float)tm[s] * (tt[s] == T_SMALL ? 0.25f : 0.125f);
+    t[4 + 4 * s] = ta[s] ? fx : 0.0f;
+    t[5 + 4 * s] = ta[s] ? fy : 0.0f;
+    t[6 + 4 * s] = ta[s] ? (float)tr[s] : 0.0f;
+    t[7 + 4 * s] = ta[s] ? fm : 0.0f;
+  }
+  t[T - 3] = (float)tcn;
+  t[T - 2] = tk == T_LS ? 1.0f : 0.0f;
+  t[T - 1] = (float)(du / 2.0);
+  const bool ls = tk == T_LS;
+  f32x4 *r4 = (f32x4 *)row;
+#pragma unroll
+  for (int q = 0; q < D / 4; q++) {
+    f32x4 o;
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int j = 4 * q + u;
+      const float w = j < 49 ? win_f(v, j < 49 ? j : 0) : 0.0f;
+      const float xc = j < 49 ? w : t[j - 49 < T ? j - 49 : 0];
+      const float xl = j < 25 ? w : (j - 25 < T ? t[j - 25 < T ? j - 25 : 0] : 0.0f);
+      o[u] = alive ? (ls ? xl : xc) : 0.0f;
+    }
+    r4[q] = o;
+  }
+}
+
+template <int NS>
+__device__ inline void row_regs_bytes_t(const Cols &c, const double *duct_col, int el, int k, int own0,
+                                        const WinRec &v, float *row, const float *xg) {
+  const int kl = k - own0;
+  uint32_t tq[NS - 1];
+  int tr[NS - 1], tm[NS - 1], tt[NS - 1], ta[NS - 1];
+#pragma unroll
+  for (int s = 0; s < NS - 1; s++) {
+    const bool nw = s < kl;  // own ships that acted before k show their new state
+    const int i = own0 + (nw ? s : s + 1);
+    tq[s] = (nw ? c.pos_cur : c.pos_old)[i * PAD + el];
+    tr[s] = (nw ? c.radar_cur : c.radar_old)[i * PAD + el];
+    tm[s] = (nw ? c.miss_cur : c.miss_old)[i * PADB + el];
+    tt[s] = c.type[i * PADB + el];
+    ta[s] = c.alive0[i * PADB + el];
+  }
+  row_build_bytes_t<NS>(c.pos_cur[k * PAD + el], c.type[k * PADB + el], c.alive0[k * PADB + el],
+                  c.radar_cur[k * PAD + el], c.miss_cur[k * PADB + el], c.tcnt[k * PAD + el], duct_col[el], tq,
+                  tr, tm, tt, ta, v, row, xg);
 }
 
 template <int NS, int NPASS4, bool NT = true>

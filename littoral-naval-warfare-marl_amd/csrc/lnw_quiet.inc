@@ -684,11 +684,9 @@ __device__ __forceinline__ void quiet_emit_units_t(const KParams &P, const KStat
   const uint32_t qm = (uint32_t)ushare[0];
   const int total = __popc(qm) * NPU;
   const int G = P.G;
-  const f32x4 *wtab = (const f32x4 *)S.winf;
   const int my_e = lane / NS, kl = lane - my_e * NS;
   const bool builder = lane < ROWS;
-  f32x4 v[12];
-  float w48 = 0.0f;
+  WinRec v;  // the row's byte record: 16 registers live across the copy-out
   auto unit_of = [&](int p, int &lp) {
     const int k = p / NPU;
     lp = p - k * NPU;
@@ -710,12 +708,10 @@ __device__ __forceinline__ void quiet_emit_units_t(const KParams &P, const KStat
       const int el = (lp >> 1) * QEPG + my_e, k = (lp & 1) * NB + kl;
       if (cu.alive0[k * PADB + el]) {
         const uint32_t p = cu.pos_cur[k * PAD + el];
-        off = ((cu.type[k * PADB + el] == T_LS ? G * G : 0) + pos_x(p) * G + pos_y(p)) * 13;
+        off = ((cu.type[k * PADB + el] == T_LS ? G * G : 0) + pos_x(p) * G + pos_y(p));
       }
     }
-#pragma unroll
-    for (int q = 0; q < 12; q++) v[q] = wtab[off + q];
-    w48 = ((const float *)(wtab + off))[48];
+    load_win(S.winf, G, off, v);
   };
   int pass = next_pass();
   if (pass < total) prefetch(pass);
@@ -725,8 +721,8 @@ __device__ __forceinline__ void quiet_emit_units_t(const KParams &P, const KStat
     const Cols cu = carve(lds_base + u * lstride, L);
     const int side = lp & 1, g = lp >> 1;
     if (builder)
-      row_regs_t<NS>(cu, duct_all[u], g * QEPG + my_e, side * NB + kl, side * NB, v, w48,
-                     stage + lane * stage_stride(NS), cu.qlut);
+      row_regs_bytes_t<NS>(cu, duct_all[u], g * QEPG + my_e, side * NB + kl, side * NB, v,
+                           stage + lane * stage_stride(NS), cu.qlut);
     wave_lds_sync();
     const int next = next_pass();
     if (next < total) prefetch(next);  // before this pass's stores (vmcnt is in issue order)
