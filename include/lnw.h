@@ -145,7 +145,15 @@ int lnw_create(const lnw_params *params, int32_t n_envs, int32_t nb, int32_t nr,
 int lnw_destroy(lnw_handle *h);
 
 /* Upload the uint8 terrain (row-major [G][G], grid[x][y]) and build the device
- * structures: radar/EW bitmask, move-feasibility table, LOS table. Synchronous. */
+ * structures: radar/EW bitmask, move-feasibility table, LOS table. Synchronous.
+ * Team sizes: each side 1..16 ships, except that a side of 16 against 10 or
+ * more (16 v 10..16, 10..16 v 16; at G = 100 and 200 alike) is refused with
+ * LNW_EUNSUPPORTED "agent count needs more LDS than a CU has": the one-lane
+ * runtime kernel's step layout, which every runtime size must be able to fall
+ * back to, then passes the 158 KiB (161 792 B) of dynamic LDS a workgroup can
+ * have (at G = 100 / 200: 16 v 9 160 192 / 160 592 B and 15 v 15 160 960 /
+ * 161 360 B load, 16 v 10 needs 161 824 / 162 224 B). The handle stays valid for
+ * lnw_destroy. */
 int lnw_load_terrain(lnw_handle *h, const uint8_t *grid_host, int32_t G);
 
 int lnw_set_rng(lnw_handle *h, int32_t mode, uint64_t seed, const double *tape_dev,

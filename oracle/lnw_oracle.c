@@ -50,6 +50,21 @@ enum {
     ORC_ERR_TLIST = 8,        /* target list overflow */
     ORC_ERR_NEUT = 16,        /* neutralized list overflow */
 };
+/* per-env step statistics (orc_fullsize_range's optional output): what the
+ * env's steps exercised, so a test can show that its inputs reach a mechanism */
+enum {
+    ORC_ST_FIX_LT8 = 0,   /* EW fixes averaged over m < 8 points */
+    ORC_ST_FIX_EQ8,       /* ... m == 8 (numpy's pairwise tree alone) */
+    ORC_ST_FIX_GT8,       /* ... m in 9..15 (the tree, then the rest in order) */
+    ORC_ST_TL_MAX,        /* longest target list an agent fired over */
+    ORC_ST_TL_PAST16,     /* firings over a list of more than 16 entries */
+    ORC_ST_BEAR_DYNEG,    /* bearings taken with dy < 0 */
+    ORC_ST_BEAR_FAR,      /* bearings taken with |dx| or |dy| > 40 */
+    ORC_ST_LS_REWARD,     /* reward evaluations of a live landing ship */
+    ORC_ST_ERR,           /* OR of the env's error flags */
+    ORC_ST_RESETS,        /* auto-resets (orc_fullsize_range) */
+    ORC_NSTATS
+};
 
 typedef struct {
     int discrete, landing_ops, aggressive, side_blue, trained_red;
@@ -85,6 +100,7 @@ typedef struct {
     int64_t tape_len, tape_pos;
     uint64_t seed, env_gid, ctr;
     uint32_t err;
+    int64_t stat[ORC_NSTATS];
 } orc_env;
 
 /* ------------------------------------------------------------------------ */
@@ -524,8 +540,9 @@ int orc_ew_range(double duct, int t_ship, int t_opp) {
     return (int)ceil(d);
 }
 
-/* numpy mean of a float64 list (pairwise_sum for n >= 8) */
-static double np_mean(const double *v, int n) {
+/* numpy mean of a float64 list (pairwise_sum for n >= 8); exported so that a
+ * test can hold it bitwise equal to numpy itself */
+double orc_np_mean(const double *v, int n) {
     double res;
     if (n < 8) {
         res = 0.0;
@@ -590,6 +607,8 @@ static void get_obs(orc_env *e, int a, double *out) {
                 if (!seen) {
                     /* calculate_bearing (combatant.py:249-263) */
                     double bearing = py_degrees(atan2((double)ddy, (double)ddx));
+                    if (ddy < 0) e->stat[ORC_ST_BEAR_DYNEG]++;
+                    if (abs(ddx) > 40 || abs(ddy) > 40) e->stat[ORC_ST_BEAR_FAR]++;
                     double distortion = rng_gauss(e);
                     if (bearing + distortion < 0)
                         bearing = bearing + distortion + 360.0;
@@ -626,7 +645,8 @@ static void get_obs(orc_env *e, int a, double *out) {
                 ne++;
             }
             if (bad) { e->err |= ORC_ERR_ZERODIV; continue; }
-            double mx = np_mean(ex, ne), my = np_mean(ey, ne);
+            e->stat[ne < 8 ? ORC_ST_FIX_LT8 : ne == 8 ? ORC_ST_FIX_EQ8 : ORC_ST_FIX_GT8]++;
+            double mx = orc_np_mean(ex, ne), my = orc_np_mean(ey, ne);
             if (!isfinite(mx) || !isfinite(my)) {
                 /* round(nan) -> ValueError, round(inf) -> OverflowError */
                 e->err |= ORC_ERR_NAN_ROUND;
@@ -815,6 +835,8 @@ static void take_action(orc_env *e, int a, const double *act, int kind, double *
     int engage = engagement_threshold > 0;
     int destroyed = 0;
     if (engage && me->tl_n > 0) {
+        if (me->tl_n > e->stat[ORC_ST_TL_MAX]) e->stat[ORC_ST_TL_MAX] = me->tl_n;
+        if (me->tl_n > 16) e->stat[ORC_ST_TL_PAST16]++;
         for (int q = 0; q < me->tl_n; q++) {
             /* check_target result only feeds the always-true
              * `target not in neutralized_units` test */
@@ -857,6 +879,7 @@ static double calculate_reward(orc_env *e, int a, int movement, int engage, int 
         reward += d;
     }
     if (u->type == T_LS) {
+        e->stat[ORC_ST_LS_REWARD]++;
         int ddx = u->x - u->lz_x, ddy = u->y - u->lz_y;
         double dl = sqrt((double)(ddx * ddx + ddy * ddy));
         if (dl > 0) {
@@ -1165,13 +1188,14 @@ int64_t orc_bench_range(const orc_params *P, const uint8_t *grid, int G, int nb,
 /* blue rows then the red rows, and the float32 rewards, done and cog, so a */
 /* 65 536-env batch is checked without holding its observations.            */
 /* pos: [E][A][2] when pos_per_env, else [A][2]. Disjoint ranges may run on */
-/* concurrent threads.                                                      */
+/* concurrent threads. stats (optional, [E][ORC_NSTATS] int64): each env's  */
+/* step statistics over the whole run (ORC_ST_*), kept in its orc_env.      */
 /* ------------------------------------------------------------------------ */
 void orc_fullsize_range(const orc_params *P, const uint8_t *grid, int G, int nb, int nr,
                         const int *types, const int *pos, int pos_per_env, const int *rand_ls,
                         uint64_t seed, int64_t E, int64_t env0, int64_t n, int S, int horizon,
                         const float *acts, const uint64_t *mult, uint64_t *hash, float *rew,
-                        int32_t *done_out, float *cog_out, float *acts_after) {
+                        int32_t *done_out, float *cog_out, float *acts_after, int64_t *stats) {
     int A = nb + nr, Db = 4 * nb + 52, Dr = 4 * nr + 52;
     orc_env *e = (orc_env *)malloc(sizeof(orc_env));
     double *act = (double *)malloc(sizeof(double) * 4 * A);
@@ -1211,10 +1235,26 @@ void orc_fullsize_range(const orc_params *P, const uint8_t *grid, int G, int nb,
             for (int a = 0; a < nr; a++) rew[se * A + nb + a] = (float)rr[a];
             done_out[se] = done;
             cog_out[se] = (float)cog;
-            if (done == 0 || e->steps_done >= horizon) orc_reset(e, types, p, rand_ls);
+            if (done == 0 || e->steps_done >= horizon) {
+                orc_reset(e, types, p, rand_ls);
+                e->stat[ORC_ST_RESETS]++;
+            }
+        }
+        if (stats) {
+            e->stat[ORC_ST_ERR] = (int64_t)e->err;
+            memcpy(stats + env * ORC_NSTATS, e->stat, sizeof(e->stat));
         }
     }
     free(e); free(act); free(kinds); free(ob); free(orr);
+}
+
+/* the same statistics of a single env (OracleEnv): out[ORC_NSTATS] */
+int orc_get_stats(const orc_env *e, int64_t *out) {
+    if (out) {
+        memcpy(out, e->stat, sizeof(e->stat));
+        out[ORC_ST_ERR] = (int64_t)e->err;
+    }
+    return ORC_NSTATS;
 }
 
 /* ------------------------------------------------------------------------ */

@@ -71,7 +71,11 @@ def lib():
         L.orc_philox.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, P]
         L.orc_fullsize_range.argtypes = [P, P, C.c_int, C.c_int, C.c_int, P, P, C.c_int, P,
                                          C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_int,
-                                         C.c_int, P, P, P, P, P, P, P]
+                                         C.c_int, P, P, P, P, P, P, P, P]
+        L.orc_np_mean.restype = C.c_double
+        L.orc_np_mean.argtypes = [P, C.c_int]
+        L.orc_get_stats.argtypes = [P, P]
+        L.orc_get_stats.restype = C.c_int
         L.orc_rollout_range.argtypes = [P, P, C.c_int, C.c_int, C.c_int, P, P, C.c_int,
                                         C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_int,
                                         C.c_int, P, P, P, P, P, P]
@@ -127,6 +131,17 @@ def move_table(grid, type_code, R, starts, thr=74):
     lib().orc_move_table(_p(grid), grid.shape[0], thr, type_code, R, _p(starts), len(starts),
                          _p(out))
     return out
+
+
+# orc_fullsize_range's / orc_get_stats' per-env step statistics (ORC_ST_*)
+STATS = ("fix_lt8", "fix_eq8", "fix_gt8", "tl_max", "tl_past16", "bear_dyneg", "bear_far",
+         "ls_reward", "err", "resets")
+
+
+def np_mean(v):
+    """The oracle's restatement of numpy.mean over a list of Python floats."""
+    v = np.ascontiguousarray(v, np.float64)
+    return lib().orc_np_mean(_p(v), len(v))
 
 
 def philox(seed, ctr, gid):
@@ -230,17 +245,25 @@ class OracleEnv:
         st.update(ducting=float(d[0]), err=int(err[0]), tape_pos=int(tp[0]), ctr=int(ctr[0]))
         return st
 
+    def stats(self):
+        """The env's step statistics so far, by name (STATS)."""
+        out = np.zeros(len(STATS), np.int64)
+        assert lib().orc_get_stats(self.e, _p(out)) == len(STATS)
+        return dict(zip(STATS, out.tolist()))
+
 
 # ---------------------------------------------------------------------------
 # golden fixtures
 # ---------------------------------------------------------------------------
 def fullsize(grid, nb, nr, types, pos, acts, mult, seed, horizon, *, pos_per_env=False,
-             rand_ls=None, landing_ops=False, trained_red=True, acts_after=False, threads=None):
+             rand_ls=None, landing_ops=False, trained_red=True, acts_after=False, stats=False,
+             threads=None):
     """orc_fullsize_range over all E envs of acts [S, E, A, 4] (float32) on a
     thread pool (ctypes releases the GIL; ranges are disjoint): per (step, env)
     the observation hash (sum bits * mult mod 2^64), float32 rewards [S, E, A],
     done [S, E] and cog [S, E]; with acts_after=True also the action rows as
-    each step left them [S, E, A, 4] (an untrained red's salvo write-back)."""
+    each step left them [S, E, A, 4] (an untrained red's salvo write-back); with
+    stats=True, last, each env's step statistics [E, len(STATS)] (int64)."""
     from concurrent.futures import ThreadPoolExecutor
     L = lib()
     S, E, A = acts.shape[:3]
@@ -256,6 +279,7 @@ def fullsize(grid, nb, nr, types, pos, acts, mult, seed, horizon, *, pos_per_env
     done = np.zeros((S, E), np.int32)
     cog = np.zeros((S, E), np.float32)
     aft = np.zeros((S, E, A, 4), np.float32) if acts_after else None
+    st = np.zeros((E, len(STATS)), np.int64) if stats else None
     threads = threads or min(16, os.cpu_count() or 1)
     chunk = (E + threads - 1) // threads
 
@@ -266,12 +290,12 @@ def fullsize(grid, nb, nr, types, pos, acts, mult, seed, horizon, *, pos_per_env
             L.orc_fullsize_range(C.byref(P), _p(grid), grid.shape[0], nb, nr, _p(types), _p(pos),
                                  int(pos_per_env), _p(rls), seed, E, e0, n, S, horizon,
                                  _p(acts), _p(mult), _p(hsh), _p(rew), _p(done), _p(cog),
-                                 _p(aft) if aft is not None else None)
+                                 _p(aft) if aft is not None else None,
+                                 _p(st) if st is not None else None)
     with ThreadPoolExecutor(threads) as ex:
         list(ex.map(run, range(threads)))
-    if acts_after:
-        return hsh, rew, done, cog, aft
-    return hsh, rew, done, cog
+    out = (hsh, rew, done, cog) + ((aft,) if acts_after else ()) + ((st,) if stats else ())
+    return out
 
 
 def rollout_env(grid, nb, nr, types, pos, acts, kinds, mult, seed, horizon, *, pos_per_env=False,

@@ -3,7 +3,9 @@ against the one-lane-per-env kernel step_kernel<0, 0> (LNW_NO_GROUP) on the
 same envs: identical observations, rewards, done, cog, written-back actions,
 state, target lists and analytics records, over episodes that fire, sink
 ships, take EW bearings and auto-reset. Both are checked against the oracle
-elsewhere (golden 8v10 replays, test_gpu_fullsize config 4)."""
+elsewhere: up to 8v10 by the golden 8v10 replays and test_gpu_fullsize's
+config 4, above it (fleets like the 12v12 here, and every LDS form of the
+group kernel) by test_gpu_team_sizes."""
 import numpy as np
 import pytest
 import torch
