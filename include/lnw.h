@@ -253,6 +253,13 @@ int lnw_set_state(lnw_handle *h, const void *src, int64_t nbytes, void *stream);
 #define LNW_KERNEL_GROUP 5         /* runtime team sizes, 16 lanes per env         */
 #define LNW_KERNEL_REFLOS 6        /* los_mode 2 (the reference's LOS work)        */
 int lnw_step_kernel(lnw_handle *h);
+/* 1 when the last lnw_step launched the units kernel compiled for the
+ * production configuration (step_units_prod_kernel: grid side 100, float32
+ * actions without row kinds, table LOS and moves, Philox draws, float32
+ * rewards, write-through rows, no diagnostics bound), 0 when it launched any
+ * other kernel. lnw_step_kernel reports LNW_KERNEL_UNITS for both units
+ * kernels; their results are the same bit for bit. */
+int lnw_step_kernel_prod(lnw_handle *h);
 /* Target-list capacity T per agent (= max(nb,nr) + max(nb,nr)^2, never overflows). */
 int lnw_tlist_cap(lnw_handle *h);
 /* Environments per workgroup of the step / observe launches (build-side launch

@@ -56,6 +56,7 @@ struct Knobs {
   bool force_group = on("LNW_FORCE_GROUP");      // (A/B) the group kernel for templated team sizes too
   bool no_split_rows = on("LNW_NO_SPLIT_ROWS");  // (A/B) row-writing contact steps keep phase S on one wave
   bool no_units = on("LNW_NO_UNITS");            // one 64-env unit per workgroup for the headline shape (A/B tests)
+  bool no_prod = on("LNW_NO_PROD");              // the generic units kernel where the production one would run (A/B tests)
   bool no_slab = on("LNW_NO_SLAB");              // no two-slab direct rows (A/B)
   bool no_xcd_remap = on("LNW_NO_XCD_REMAP");    // KParams.xcd_remap off (A/B)
   // LNW_GROUP_MARCH=1: the group kernel marches its pair LOS over the LDS
@@ -91,6 +92,7 @@ struct lnw_handle {
   bool units_fit = false;   // UNITS blocks of the step layout fit one workgroup
   bool contact = false;  // lnw_set_variant: contact-heavy phase-S code in the templated kernels
   int last_kernel = LNW_KERNEL_NONE;     // lnw_step_kernel: what the last lnw_step launched
+  bool last_prod = false;                // lnw_step_kernel_prod: it was step_units_prod_kernel
   bool has_medium = false;               // the spawn spec has medium ships (runtime-size kernels only)
   unsigned long long terrain_hash = 0;   // FNV-1a of the loaded grid (state snapshots name their terrain)
   uint32_t *d_mask2 = nullptr, *d_mvtab = nullptr, *d_lostab = nullptr;
@@ -207,7 +209,7 @@ constexpr int TEAM_THREADS = EPW == WAVE ? 2 * WAVE : WAVE;  // step_kernel<N, N
 // rows of STEP_KERNELS; the plain n-v-n kernels sit at SK_2V2 + 2 * (n - 2) + contact
 enum StepK {
   SK_GENERIC, SK_REFLOS, SK_GROUP, SK_2V2, SK_2V2_CONTACT, SK_3V3, SK_3V3_CONTACT, SK_4V4, SK_4V4_CONTACT,
-  SK_4V4_SPLIT, SK_4V4_SLAB, SK_UNITS, SK_COUNT
+  SK_4V4_SPLIT, SK_4V4_SLAB, SK_UNITS, SK_UNITS_PROD, SK_COUNT
 };
 const KernelRow<StepFn> STEP_KERNELS[] = {
     {step_kernel<0, 0>, LNW_KERNEL_GENERIC, WAVE, GROUP_LDS_MAX},
@@ -225,6 +227,8 @@ const KernelRow<StepFn> STEP_KERNELS[] = {
     {step_kernel<4, 4, false, false, 1, false, true>, LNW_KERNEL_TEAM, TEAM_THREADS, GROUP_LDS_MAX},
     // 4 units of 64 envs per workgroup, one workgroup per CU (step_kernel UN)
     {step_kernel<4, 4, false, false, UNITS>, LNW_KERNEL_UNITS, TEAM_THREADS * UNITS, UNITS_LDS_MAX},
+    // the same compiled for the production configuration (ProdCfg, prod_config)
+    {step_units_prod_kernel, LNW_KERNEL_UNITS, TEAM_THREADS * UNITS, UNITS_LDS_MAX},
 };
 static_assert(sizeof STEP_KERNELS / sizeof STEP_KERNELS[0] == SK_COUNT, "one row per StepK");
 
@@ -276,6 +280,28 @@ size_t step_launch_lds_bytes(const lnw_handle *h, int epw) {
   return step_lds_bytes(h, step_qdirect(h, epw) ? (epw * h->nb < WAVE ? epw * h->nb : WAVE) : 0);
 }
 
+// The production configuration, checked value by value against the launch about
+// to be made. What ProdCfg (lnw_kernels.hip) compiles into
+// step_units_prod_kernel: grid side 100; float32 action rows without row
+// kinds; table LOS and moves; no LNW_DEBUG_SKIP bit; no LNW_PROF buffer (team
+// sizes, 7x7 windows and 64-env units are the units kernel's own conditions,
+// plan_step); a group that a measurement build leaves runtime
+// (LNW_PROD_GROUPS) is not checked. And what the kernel still reads at run time
+// but a production launch has: no work counters or analytics channels, Philox
+// draws, float32 rewards, write-through rows. Those keep the kernel to the
+// configuration its tests run it in.
+bool prod_config(const lnw_handle *h, int act_dtype, bool row_kind) {
+  const lnw_analytics &an = h->ana;
+  const bool ana = an.heatmap || an.coldmap || an.launch || an.eng_log || an.ew_log;
+  auto ok = [](int group, bool holds) { return !(ProdCfg::GROUPS & group) || holds; };
+  return ok(PG_GRID, h->G == PROD_G && h->W16 == (PROD_G + 15) / 16) &&
+         ok(PG_ACTIONS, act_dtype == LNW_ACT_F32 && !row_kind) &&
+         ok(PG_MODES, h->params.los_mode == 0 && h->params.move_mode == 0) &&
+         ok(PG_DEBUG, h->knobs.dbg_skip == 0) && ok(PG_PROF, !h->knobs.prof) &&
+         // the rest of the production configuration, which the kernel reads at run time
+         !h->ctr && !ana && h->kp.rng_mode == LNW_RNG_PHILOX && !h->kp.rew_f64 && h->store_wt;
+}
+
 // One step launch, decided: the kernel's table row, its launch shape, KParams'
 // qdirect and the number of LNW_PROF records the launch writes (nwg).
 struct StepPlan {
@@ -285,7 +311,7 @@ struct StepPlan {
   bool qdirect;
 };
 
-StepPlan plan_step(const lnw_handle *h, int epw, bool no_obs) {
+StepPlan plan_step(const lnw_handle *h, int epw, bool no_obs, int act_dtype, bool row_kind) {
   const Knobs &kn = h->knobs;
   const int los = h->params.los_mode;
   const bool cw = h->contact;
@@ -301,7 +327,8 @@ StepPlan plan_step(const lnw_handle *h, int epw, bool no_obs) {
   StepPlan p;
   p.qdirect = step_qdirect(h, epw);
   int r = group ? SK_GROUP : SK_GENERIC;
-  if (units) r = SK_UNITS;
+  // (LNW_NO_PROD keeps the generic units kernel, beside LNW_NO_UNITS)
+  if (units) r = !kn.no_prod && prod_config(h, act_dtype, row_kind) ? SK_UNITS_PROD : SK_UNITS;
   else if (los == 2) r = SK_REFLOS;
   // the contact variant with phase S split by side (LNW_NO_SPLIT_ROWS: only for steps without rows, A/B)
   else if (templated && h->nb == 4 && cw && los == 0 && (no_obs || !kn.no_split_rows)) r = SK_4V4_SPLIT;
@@ -712,7 +739,7 @@ int lnw_step(lnw_handle *h, void *actions_dev, int32_t action_dtype, const uint8
   k.store_wt = h->store_wt;
   KState s;
   if (int rc = launch_state(h, s)) return rc;
-  const StepPlan p = plan_step(h, k.epw, k.no_obs != 0);
+  const StepPlan p = plan_step(h, k.epw, k.no_obs != 0, action_dtype, row_kind_dev != nullptr);
   k.qdirect = p.qdirect ? 1 : 0;
   hipStream_t st = (hipStream_t)stream;
   if (h->knobs.prof) {
@@ -732,6 +759,7 @@ int lnw_step(lnw_handle *h, void *actions_dev, int32_t action_dtype, const uint8
     }
   }
   h->last_kernel = p.row->code;
+  h->last_prod = p.row == &STEP_KERNELS[SK_UNITS_PROD];
   p.row->fn<<<dim3(p.grid), dim3(p.block), p.lds, st>>>(k, s, actions_dev, row_kind_dev, obs_blue_dev, obs_red_dev,
                                                          rew_blue_dev, rew_red_dev, done_dev, cog_dev);
   HIPCHK(hipGetLastError());
@@ -819,6 +847,8 @@ int lnw_state_field(lnw_handle *h, int32_t field, void **dev_ptr, int64_t *nbyte
 int lnw_tlist_cap(lnw_handle *h) { return h ? h->T : LNW_EINVAL; }
 
 int lnw_step_kernel(lnw_handle *h) { return h ? h->last_kernel : LNW_EINVAL; }
+
+int lnw_step_kernel_prod(lnw_handle *h) { return h ? (h->last_prod ? 1 : 0) : LNW_EINVAL; }
 
 // ---- whole-state snapshots (lnw_state_bytes / lnw_get_state / lnw_set_state)
 // Snapshot layout: a 128-byte header (below), then the LNW_NFIELDS state

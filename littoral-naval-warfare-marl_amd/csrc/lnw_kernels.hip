@@ -3179,11 +3179,64 @@ extern __shared__ __attribute__((aligned(16))) char lds_dyn[];
 // observation passes go through one workgroup-wide queue that every free wave
 // of a quiet unit serves, so the CU's units finish their stream together
 // instead of 4-5 us apart (the spread of separate workgroups on one CU).
-template <int NB, int NR, bool CW, bool REFW, int UN, bool PS, bool SL>
+//
+// CF: where the launch's configuration comes from. Everything below reads it
+// through P, S and row_kind as CF::fix leaves them:
+//   RuntimeCfg  the arguments as they are (every step_kernel instantiation);
+//   ProdCfg     the arguments with the values of the production configuration
+//               stated as constants (step_units_prod_kernel), so the tests of
+//               them, the arithmetic on them and the code behind their other
+//               values fold away. No rule is written twice: the trait replaces
+//               reads, the bodies are the same text.
+struct RuntimeCfg {
+  static __device__ __forceinline__ void fix(const KParams &, KState &, const uint8_t *&) {}
+};
+
+// The production configuration of the 4v4 units kernel, group by group
+// (profiles/units_prod.md has what each is worth). plan_step (lnw_host.inc,
+// prod_config) checks every value fixed here before it takes the kernel.
+// LNW_PROD_GROUPS (a build-time mask, measurements only) leaves groups runtime.
+#ifndef LNW_PROD_GROUPS
+#define LNW_PROD_GROUPS 0x3f
+#endif
+enum {
+  PG_SHAPE = 1,    // what the units kernel's launch implies: 4v4, 7x7 windows, 64 envs per unit
+  PG_GRID = 2,     // grid side 100: W16, the mask's words, the LDS layout, the x / G table's bounds
+  PG_ACTIONS = 4,  // float32 action rows without row kinds
+  PG_MODES = 8,    // los_mode 0, move_mode 0
+  PG_DEBUG = 16,   // no LNW_DEBUG_SKIP bit
+  PG_PROF = 32,    // no LNW_PROF buffer
+};
+// (Philox draws, float32 rewards and write-through rows were stated too and the
+// compiler produced the same code with and without them: they stay runtime
+// reads. prod_config still asks for them, so the kernel runs only in the
+// configuration it is tested in.)
+constexpr int PROD_G = 100;
+struct ProdCfg {
+  static constexpr int GROUPS = LNW_PROD_GROUPS;
+  // KParams' values are stated (the host has checked them), not written over a
+  // copy: the struct stays in the argument segment, where its tables are
+  // indexed at run time (a private copy of it was 480 B per lane of scratch).
+  // KState and the pointer are step_body's own copies and are written.
+  static __device__ __forceinline__ void fix(const KParams &P, KState &S, const uint8_t *&row_kind) {
+    if (GROUPS & PG_SHAPE)
+      __builtin_assume(P.nb == 4 && P.nr == 4 && P.A == 8 && P.wc[0] == 49 && P.wc[1] == 49 && P.epw == EPW);
+    if (GROUPS & PG_GRID) __builtin_assume(P.G == PROD_G && P.W16 == (PROD_G + 15) / 16);
+    if (GROUPS & PG_ACTIONS) __builtin_assume(P.act_dtype == LNW_ACT_F32);
+    if (GROUPS & PG_MODES) __builtin_assume(P.los_mode == 0 && P.move_mode == 0);
+    if (GROUPS & PG_DEBUG) __builtin_assume(P.dbg_skip == 0);
+    if (GROUPS & PG_SHAPE) S.nmax = 4;
+    if (GROUPS & PG_PROF) S.prof = nullptr;
+    if (GROUPS & PG_ACTIONS) row_kind = nullptr;
+  }
+};
+
+template <int NB, int NR, bool CW, bool REFW, int UN, bool PS, bool SL, class CF = RuntimeCfg>
 __device__ __forceinline__ void step_body(
     const KParams &P, KState S, void *actions, const uint8_t *row_kind, float *obs_b, float *obs_r,
     float *rew_b, float *rew_r, int32_t *done_out, float *cog_out, unsigned long long t_entry = 0) {
   static_assert(UN == 1 || (NB > 0 && EPW == WAVE && !REFW), "units need the two-wave templated kernel");
+  CF::fix(P, S, row_kind);
   const int unit = UN > 1 ? (int)(threadIdx.x / (2 * WAVE)) : 0;
   const int lane = threadIdx.x & (WAVE - 1);
   const int wid = UN > 1 ? (int)((threadIdx.x / WAVE) & 1) : (int)(threadIdx.x / WAVE);
@@ -3582,6 +3635,21 @@ __global__ __launch_bounds__(NB > 0 && EPW == WAVE ? 2 * WAVE * UN : WAVE, NB > 
   kernarg_lines_prefetch();
   step_body<NB, NR, CW, REFW, UN, PS, SL>(P, S, actions, row_kind, obs_b, obs_r, rew_b, rew_r, done_out, cog_out);
 #endif
+}
+
+// The units kernel (step_kernel<4, 4, false, false, UNITS>) compiled for the
+// production configuration (ProdCfg): the same body, launch shape, LDS and
+// arguments, taken by plan_step only when the handle's values are the ones
+// ProdCfg fixes. Under a name of its own: the generic units kernel stays as it
+// is, with its resource pins (tests/test_step_args_cpu.py), for every other
+// configuration.
+__global__ __launch_bounds__(2 * WAVE * UNITS, 2) void step_units_prod_kernel(
+    KParams P, KState S, void *actions, const uint8_t *row_kind, float *obs_b, float *obs_r,
+    float *rew_b, float *rew_r, int32_t *done_out, float *cog_out) {
+  static_assert(EPW == WAVE, "the units kernels run 64-env units");
+  kernarg_lines_prefetch();
+  step_body<4, 4, false, false, UNITS, false, false, ProdCfg>(P, S, actions, row_kind, obs_b, obs_r, rew_b, rew_r,
+                                                              done_out, cog_out);
 }
 
 #include "lnw_group.inc"

@@ -30,7 +30,7 @@ SYMBOLS = [
     "lnw_set_counters",
     "lnw_los_batch", "lnw_astar_batch", "lnw_move_batch", "lnw_path_query", "lnw_los_query", "lnw_copy",
     "lnw_fill_uniform_f32", "lnw_hit_tables", "lnw_set_analytics", "lnw_actor_features",
-    "lnw_state_bytes", "lnw_get_state", "lnw_set_state", "lnw_step_kernel",
+    "lnw_state_bytes", "lnw_get_state", "lnw_set_state", "lnw_step_kernel", "lnw_step_kernel_prod",
     "lnw_policy_act", "lnw_rollout_post", "lnw_qnet_act",
     "lnw_qlearn_workspace_bytes", "lnw_qnet_grad", "lnw_qnet_adam",
     "lnw_ppolearn_workspace_bytes", "lnw_ppo_grad", "lnw_ppo_clip_adam",
@@ -39,6 +39,9 @@ SYMBOLS = [
 ]
 # lnw_ppo_sample's Philox counter words 2 and 3, and its largest batch (include/lnw.h)
 LNW_SAMPLE_CTR2, LNW_SAMPLE_CTR3, LNW_SAMPLE_MAX_BATCH = 0x13198A2E, 0x03707344, 131072
+
+# getters added without an ABI version change (load)
+ADDITIVE = ("lnw_step_kernel_prod",)
 
 # lnw_step_kernel codes (include/lnw.h LNW_KERNEL_*)
 (KERNEL_NONE, KERNEL_GENERIC, KERNEL_TEAM, KERNEL_TEAM_CONTACT, KERNEL_UNITS, KERNEL_GROUP,
@@ -202,6 +205,7 @@ def load(path=None):
         "lnw_get_state": ([P, P, I64, P], C.c_int),
         "lnw_set_state": ([P, P, I64, P], C.c_int),
         "lnw_step_kernel": ([P], C.c_int),
+        "lnw_step_kernel_prod": ([P], C.c_int),
         "lnw_policy_act": ([C.POINTER(PolicyArgs), P], C.c_int),
         "lnw_rollout_post": ([C.POINTER(RolloutPostArgs), P], C.c_int),
         "lnw_qnet_act": ([C.POINTER(QnetArgs), P], C.c_int),
@@ -220,6 +224,10 @@ def load(path=None):
         "lnw_ppo_sample": ([C.POINTER(PpoSampleArgs), P], C.c_int),
     }
     for name, (args, res) in sig.items():
+        # (a library built before an additive getter existed still loads, for
+        # A/B runs under LNW_LIB; calling the getter on it raises)
+        if name in ADDITIVE and not hasattr(L, name):
+            continue
         f = getattr(L, name)
         f.argtypes = args
         f.restype = res

@@ -388,6 +388,12 @@ class BatchedGame:
         _abi.KERNEL_*): build-side launch shape, for tests and diagnostics."""
         return self.L.lnw_step_kernel(self.h)
 
+    def step_kernel_prod(self):
+        """True when the last step() ran the units kernel compiled for the
+        production configuration (lnw_step_kernel_prod), False for any other
+        kernel, the generic units kernel included."""
+        return self.L.lnw_step_kernel_prod(self.h) == 1
+
     def get_state(self, device="cpu"):
         """Whole-state snapshot (lnw_get_state) as a uint8 tensor on `device`:
         every state field, the auto-reset's spawn spec and the RNG mode/seed.

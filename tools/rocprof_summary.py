@@ -33,6 +33,15 @@ def short(name):
     return n.split("(")[0]
 
 
+# the step kernels by name: every step_kernel<...> instantiation, the group kernel and
+# the units kernel compiled for the production configuration
+STEP_NAMES = ("step_kernel", "step_group_kernel", "step_units_prod_kernel")
+
+
+def is_step(name):
+    return any(n in name for n in STEP_NAMES)
+
+
 def counters(d, stem):
     path = os.path.join(OUT, d, f"{stem}_counter_collection.csv")
     acc = defaultdict(list)
@@ -40,7 +49,7 @@ def counters(d, stem):
         return {}
     with open(path) as f:
         for r in csv.DictReader(f):
-            if "step_kernel" not in r["Kernel_Name"] and "step_group_kernel" not in r["Kernel_Name"]:
+            if not is_step(r["Kernel_Name"]):
                 continue
             acc[(r["Dispatch_Id"], r["Counter_Name"])].append(float(r["Counter_Value"]))
     per = defaultdict(list)
@@ -169,7 +178,7 @@ def main():
         avg = float(r["AverageNs"]) / 1e3
         lines.append(f"| {short(r['Name'])} | {r['Calls']} | {avg:.1f} | {float(r['MinNs']) / 1e3:.1f} | "
                      f"{float(r['MaxNs']) / 1e3:.1f} | {float(r['Percentage']):.1f} |")
-        if ("step_kernel" in r["Name"] or "step_group_kernel" in r["Name"]) and step_avg is None:
+        if is_step(r["Name"]) and step_avg is None:
             step_avg, step_name = avg, short(r["Name"])
     pmc = {}
     for sub in ("fetch", "write", "sq", "sq2"):
