@@ -23,6 +23,7 @@ import math
 import numpy as np
 
 import _oracle
+from _spawns import grid as _grid
 
 DUCT_DRAW = 0.9  # np.random.beta's tape value: ducting 1.9, EW range small on large 30 cells
 
@@ -98,7 +99,7 @@ def targets(c, mean):
 def oracle_step(c):
     """One step of the layout on the oracle: its step() record and the OracleEnv."""
     n = len(c["blue"])
-    o = _oracle.OracleEnv(_oracle.load_fixture("grids.npz")["grid100"], n, 1, landing_ops=False)
+    o = _oracle.OracleEnv(_grid(100), n, 1, landing_ops=False)
     o.set_tape(tape(c))
     o.reset([_oracle.T_SMALL] * n + [_oracle.T_LARGE], positions(c))
     r = o.step(np.zeros((n + 1, 4), np.float32), np.full(n + 1, _oracle.K_F32, np.int32))

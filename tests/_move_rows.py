@@ -20,8 +20,8 @@ import functools
 import numpy as np
 
 import _oracle
+from _spawns import grid, ref_spawns
 
-REF_SPAWNS = [(6, 61), (10, 81), (8, 70), (11, 58), (98, 48), (98, 52), (98, 56), (96, 52)]
 STEPS = 12
 E_SIM = 512
 SEED = 20
@@ -44,11 +44,6 @@ TIE_BAND = 4e-5  # move_cell_f32_fast's distance from a half-integer
 TIE_MARGIN = 4e-6  # the polynomials' error on a coordinate (3e-5 is the proven bound; typical 1e-6)
 
 
-@functools.lru_cache(maxsize=None)
-def grid():
-    return _oracle.load_fixture("grids.npz")["grid100"]
-
-
 def types_of(team):
     b, r, _ = TEAMS[team]
     return [TYPE_CODES[t] for t in b + r]
@@ -66,7 +61,7 @@ def positions(team):
     nb = len(TEAMS[team][0])
     g = grid()
     rng = np.random.default_rng([SEED, nb, 1])
-    pos = np.array([REF_SPAWNS[:nb] + REF_SPAWNS[4:4 + nb]] * E_SIM, np.int32)
+    pos = np.array([ref_spawns(nb)] * E_SIM, np.int32)
     for b, kind in enumerate(BLOCKS):
         e0 = 64 * b
         if kind == "melee":
@@ -161,14 +156,10 @@ def simulate(team):
     types = types_of(team)
     pos = positions(team)
     acts, cls = rows(team)
-    D = 4 * nb + 52
     kinds = np.full(A, _oracle.K_F32, np.int32)
     S, E = STEPS, E_SIM
-    out = dict(obs_blue=np.zeros((S, E, nb, D), np.float32), obs_red=np.zeros((S, E, nb, D), np.float32),
-               rew_blue=np.zeros((S, E, nb)), rew_red=np.zeros((S, E, nb)),
-               done=np.zeros((S, E), np.int32), cog=np.zeros((S, E)),
-               acts_after=np.zeros((S, E, A, 4), np.float32),
-               pos_before=np.zeros((S, E, A, 2), np.int32), pos_after=np.zeros((S, E, A, 2), np.int32),
+    out = _oracle.new_record(S, E, nb, nb)
+    out.update(pos_before=np.zeros((S, E, A, 2), np.int32), pos_after=np.zeros((S, E, A, 2), np.int32),
                alive_before=np.zeros((S, E, A), bool), err=np.zeros((S, E), np.uint32))
     for e in range(E):
         o = _oracle.OracleEnv(g, nb, nb, landing_ops=landing)
@@ -178,11 +169,7 @@ def simulate(team):
         for s in range(S):
             out["pos_before"][s, e], out["alive_before"][s, e] = ag["pos"], ag["alive"] != 0
             r = o.step(acts[s, e], kinds)
-            for k in ("obs_blue", "obs_red"):
-                out[k][s, e] = r[k].astype(np.float32)
-            out["rew_blue"][s, e], out["rew_red"][s, e] = r["rew_blue"], r["rew_red"]
-            out["done"][s, e], out["cog"][s, e] = r["done"], r["cog"]
-            out["acts_after"][s, e] = r["actions_after"].astype(np.float32)
+            _oracle.record_step(out, s, e, r)
             ag = o.agents()
             out["pos_after"][s, e] = ag["pos"]
             out["err"][s, e] = o.env_state()["err"]

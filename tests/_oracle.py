@@ -252,6 +252,29 @@ class OracleEnv:
         return dict(zip(STATS, out.tolist()))
 
 
+RECORD_KEYS = ("obs_blue", "obs_red", "rew_blue", "rew_red", "done", "cog", "acts_after")
+
+
+def new_record(steps, E, nb, nr, act_dtype=np.float32):
+    """The output arrays of a record [steps, E, ...] of OracleEnv.step results
+    (RECORD_KEYS): observation rows as float32, rewards and cog as float64."""
+    A = nb + nr
+    return dict(obs_blue=np.zeros((steps, E, nb, 4 * nb + 52), np.float32),
+                obs_red=np.zeros((steps, E, nr, 4 * nr + 52), np.float32),
+                rew_blue=np.zeros((steps, E, nb)), rew_red=np.zeros((steps, E, nr)),
+                done=np.zeros((steps, E), np.int32), cog=np.zeros((steps, E)),
+                acts_after=np.zeros((steps, E, A, 4), act_dtype))
+
+
+def record_step(rec, s, e, r):
+    """Stores the OracleEnv.step result r as step s of env e."""
+    for k in ("obs_blue", "obs_red"):
+        rec[k][s, e] = r[k].astype(np.float32)
+    rec["rew_blue"][s, e], rec["rew_red"][s, e] = r["rew_blue"], r["rew_red"]
+    rec["done"][s, e], rec["cog"][s, e] = r["done"], r["cog"]
+    rec["acts_after"][s, e] = r["actions_after"].astype(rec["acts_after"].dtype)
+
+
 # ---------------------------------------------------------------------------
 # golden fixtures
 # ---------------------------------------------------------------------------

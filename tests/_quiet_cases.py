@@ -17,8 +17,8 @@ import math
 import numpy as np
 
 import _oracle
+from _spawns import grid as _grid, ref_spawns
 
-REF_SPAWNS = [(6, 61), (10, 81), (8, 70), (11, 58), (98, 48), (98, 52), (98, 56), (96, 52)]
 DUCTS = (1.0, 1.37, 1.99)  # across the reference's 1 <= 1 + Beta(1, 3) < 2
 KS = (-2, -1, 0, 1, 2, 3)
 DIRS = ("x", "y", "diag")
@@ -190,8 +190,7 @@ def layout(nb, epw, seed, grid, units=False):
         lanes = [0, epw - 1, epw // 2]
         probes = [w * epw + lanes[(w + seed) % 3] for w in range(2)] + [E - 1]
     A = 2 * nb
-    spawns = REF_SPAWNS[:nb] + REF_SPAWNS[4:4 + nb]
-    pos = np.array([spawns] * E, np.int32)
+    pos = np.array([ref_spawns(nb)] * E, np.int32)
     duct = np.full(E, np.nan)
     S = 45
     acts = rng.random((S, E, A, 4), dtype=np.float32)
@@ -283,11 +282,6 @@ def oracle_loud(before, after, ctr_before, ctr_after):
 # ---------------------------------------------------------------------------
 # the oracle over a layout
 # ---------------------------------------------------------------------------
-@functools.lru_cache(maxsize=4)
-def _grid(G):
-    return _oracle.load_fixture("grids.npz")[f"grid{G}"]
-
-
 @functools.lru_cache(maxsize=8)
 def simulate(nb, epw, G, seed, steps, units=False, red=None, trained_red=True, horizon=0,
              landing_ops=False):
@@ -302,13 +296,9 @@ def simulate(nb, epw, G, seed, steps, units=False, red=None, trained_red=True, h
     pos, duct, acts, probes = layout(nb, epw, seed, grid, units)
     E, A = pos.shape[0], 2 * nb
     types = [_oracle.T_LARGE] * nb + [TYPE_CODES[t] for t in (red or ("large",) * nb)]
-    D = 4 * nb + 52
     kinds = np.full(A, _oracle.K_F32, np.int32)
-    out = dict(obs_blue=np.zeros((steps, E, nb, D), np.float32), obs_red=np.zeros((steps, E, nb, D), np.float32),
-               rew_blue=np.zeros((steps, E, nb)), rew_red=np.zeros((steps, E, nb)),
-               done=np.zeros((steps, E), np.int32), cog=np.zeros((steps, E)),
-               acts_after=np.zeros((steps, E, A, 4), np.float32),
-               loud=np.zeros((steps, E), bool), quiet=np.zeros((steps, E), bool),
+    out = _oracle.new_record(steps, E, nb, nb)
+    out.update(loud=np.zeros((steps, E), bool), quiet=np.zeros((steps, E), bool),
                mutant_quiet=np.zeros((len(MUTANTS), steps, E), bool),
                near2=np.zeros((steps, E), np.int64), r2=np.zeros((steps, E), np.int64),
                dead_inside=np.zeros((steps, E), bool), reset=np.zeros((steps, E), bool),
@@ -324,11 +314,7 @@ def simulate(nb, epw, G, seed, steps, units=False, red=None, trained_red=True, h
             if not horizon:
                 before, st0 = o.agents(), o.env_state()
             r = o.step(acts[s, e], kinds)
-            for k in ("obs_blue", "obs_red"):
-                out[k][s, e] = r[k].astype(np.float32)
-            out["rew_blue"][s, e], out["rew_red"][s, e] = r["rew_blue"], r["rew_red"]
-            out["done"][s, e], out["cog"][s, e] = r["done"], r["cog"]
-            out["acts_after"][s, e] = r["actions_after"].astype(np.float32)
+            _oracle.record_step(out, s, e, r)
             t += 1
             if horizon:  # (the verdicts below are for runs without resets)
                 if r["done"] == 0 or t >= horizon:

@@ -17,7 +17,7 @@ import functools
 import numpy as np
 
 import _oracle
-from _fullsize_util import _grids, _mult
+from _spawns import box_positions, grid as _grid, hash_mult
 
 STEPS, HORIZON = 30, 25
 SEED = 11
@@ -68,23 +68,11 @@ TLIST_STEPS = (3, 26, 30)
 
 
 def grid(cs):
-    g100, g200 = _grids()
-    return g100 if cs["G"] == 100 else g200
+    return _grid(cs["G"])
 
 
 def types(cs):
     return [TYPE[t] for t in cs["blue"] + cs["red"]]
-
-
-def box_positions(grid, E, nb, nr, seed, box_b, box_r):
-    """tests/test_gpu_group.py's spawns: per env, every ship on a water cell of
-    its side's box."""
-    rng = np.random.default_rng(seed)
-    water = lambda x0, x1, y0, y1: [(x, y) for x in range(x0, x1) for y in range(y0, y1)
-                                    if grid[x, y] <= 74]
-    wb, wr = water(*box_b), water(*box_r)
-    return np.array([[wb[i] for i in rng.integers(0, len(wb), nb)] +
-                     [wr[i] for i in rng.integers(0, len(wr), nr)] for _ in range(E)], np.int32)
 
 
 def positions(cs):
@@ -102,7 +90,7 @@ def actions(cs):
 
 def mult(cs):
     nb, nr = len(cs["blue"]), len(cs["red"])
-    return _mult(nb * (4 * nb + 52) + nr * (4 * nr + 52), seed=9)
+    return hash_mult(nb * (4 * nb + 52) + nr * (4 * nr + 52), seed=9)
 
 
 def _hash(ob, orr, m):

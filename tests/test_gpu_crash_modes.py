@@ -15,12 +15,14 @@ import numpy as np
 import pytest
 import torch
 
+import _device as D
 import _oracle
-from test_oracle_crash_cpu import EXC_BIT, FX, META
+from _crash_cases import EXC_BIT, FX, META
+from _device import REW_TOL
+from _spawns import REF_SPAWNS, box_positions, grid as _grid
 
 pytestmark = pytest.mark.gpu
 
-REW_TOL = 1e-5
 CASES = sorted(META)
 # variant -> (contact variant, environment knobs read at lnw_create, envs, epw, kernel code)
 VARIANTS = {
@@ -34,23 +36,14 @@ VARIANTS = {
 
 @pytest.fixture(scope="module")
 def grid():
-    return np.load(_oracle.GOLDEN + "/grids.npz")["grid100"]
+    return _grid(100)
 
 
 def _game(grid, variant, monkeypatch, E):
-    from lnw.batched import BatchedGame
     from lnw.config import Scenario
     contact, knobs, _, epw, _ = VARIANTS[variant]
-    for k, v in knobs.items():
-        monkeypatch.setenv(k, v)
-    g = BatchedGame(E, ["small"] * 4, ["large"] * 4, scenario=Scenario(landing_ops=False), grid=grid,
-                    reward_dtype=torch.float64, seed=1234)
-    for k in knobs:
-        monkeypatch.delenv(k)
-    g.set_variant(contact)
-    if epw:
-        assert g.set_epw(epw) == epw
-    return g
+    return D.make_game(monkeypatch, E, ["small"] * 4, ["large"] * 4, Scenario(landing_ops=False), grid, 1234,
+                       env=knobs, epw=epw, contact=contact, reward_dtype=torch.float64)
 
 
 def _compare(g, res, oracles, act_after, s, ctx):
@@ -128,11 +121,10 @@ def test_nonfinite_action_rows_vs_oracle(grid, variant, dtype, monkeypatch):
     quiet path, whose test sends non-finite rows to phase S) and half in
     contact, 10 Philox steps: every output, error bit and state field equal to
     the oracle's."""
-    from test_gpu_parity import REF_SPAWNS, _melee_positions
     E = VARIANTS[variant][2]
     g = _game(grid, variant, monkeypatch, E)
     pos = np.array([REF_SPAWNS] * E, np.int32)
-    pos[E // 2:] = _melee_positions(grid, E - E // 2, 4, 4, seed=11)
+    pos[E // 2:] = box_positions(grid, E - E // 2, 4, 4, seed=11)
     g.reset(positions=pos[0], pos_per_env=torch.from_numpy(pos))
     oracles = []
     for e in range(E):

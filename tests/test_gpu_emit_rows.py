@@ -9,11 +9,10 @@ landing ship on red, which puts the landing-ship row layout through the
 compile-time row select."""
 import numpy as np
 import pytest
-import torch
 
+import _device as D
 import _oracle
-from _oracle import load_fixture
-from test_gpu_parity import REW_TOL, _melee_positions
+from _spawns import box_positions, grid as _grid
 
 pytestmark = pytest.mark.gpu
 
@@ -28,34 +27,30 @@ CASES = {
 def _inputs(name):
     blue, red = CASES[name]
     nb, nr = len(blue), len(red)
-    grid = load_fixture("grids.npz")["grid100"]
-    pos = _melee_positions(grid, E, nb, nr, seed=nb)
+    grid = _grid(100)
+    pos = box_positions(grid, E, nb, nr, seed=nb)
     rng = np.random.default_rng(100 + nb)
     acts = [rng.random((E, nb + nr, 4)).astype(np.float32) for _ in range(S)]
     return grid, pos, acts
 
 
 def _oracle_run(name, grid, pos, acts):
-    """[S][E] step results of the oracle stepping the same envs."""
+    """The oracle's record [S, E] of stepping the same envs."""
     blue, red = CASES[name]
-    A = len(blue) + len(red)
-    oracles = []
+    nb, nr = len(blue), len(red)
+    rec = _oracle.new_record(S, E, nb, nr)
+    kinds = np.full(nb + nr, _oracle.K_F32, np.int32)
     for e in range(E):
-        o = _oracle.OracleEnv(grid, len(blue), len(red))
+        o = _oracle.OracleEnv(grid, nb, nr)
         o.set_philox(SEED, e)
         o.reset([CODES[t] for t in blue + red], pos[e])
-        oracles.append(o)
-    kinds = np.full(A, _oracle.K_F32, np.int32)
-    return [[o.step(act[e], kinds) for e, o in enumerate(oracles)] for act in acts]
-
-
-def _zero_rows(want, side):
-    return sum(int((~r[side].any(axis=1)).sum()) for step in want for r in step)
+        for s, act in enumerate(acts):
+            _oracle.record_step(rec, s, e, o.step(act[e], kinds))
+    return rec
 
 
 @pytest.mark.parametrize("name", sorted(CASES))
-def test_philox_emission_vs_oracle(name):
-    from lnw.batched import BatchedGame
+def test_philox_emission_vs_oracle(name, monkeypatch):
     from lnw.config import Scenario
     blue, red = CASES[name]
     grid, pos, acts = _inputs(name)
@@ -63,20 +58,10 @@ def test_philox_emission_vs_oracle(name):
     # a sunk ship's row is all zeros: each side must show some, or a kernel that
     # never zeroes a dead row would pass
     for side in ("obs_blue", "obs_red"):
-        assert _zero_rows(want, side) > 0, (name, side)
-    g = BatchedGame(E, blue, red, scenario=Scenario(landing_ops=False), grid=grid, seed=SEED)
-    assert g.set_epw(64) == 64  # one full wave of envs per workgroup: rows leave during phase S
-    g.reset(positions=pos[0], pos_per_env=torch.from_numpy(pos))
+        assert (~want[side].any(axis=-1)).sum() > 0, (name, side)
+    # one full wave of envs per workgroup: rows leave during phase S
+    g = D.make_game(monkeypatch, E, blue, red, Scenario(landing_ops=False), grid, SEED, epw=64)
+    D.start(g, pos)
     for s, act in enumerate(acts):
-        out = g.step(torch.from_numpy(act).cuda())
-        ob, orr = out["obs_blue"].cpu().numpy(), out["obs_red"].cpu().numpy()
-        rb, rr = out["rew_blue"].cpu().numpy(), out["rew_red"].cpu().numpy()
-        dn = out["done"].cpu().numpy()
-        for e in range(E):
-            r = want[s][e]
-            assert np.array_equal(ob[e], r["obs_blue"].astype(np.float32)), (s, e, "obs_blue")
-            assert np.array_equal(orr[e], r["obs_red"].astype(np.float32)), (s, e, "obs_red")
-            assert np.allclose(rb[e], r["rew_blue"], rtol=0, atol=REW_TOL), (s, e, "rew_blue")
-            assert np.allclose(rr[e], r["rew_red"], rtol=0, atol=REW_TOL), (s, e, "rew_red")
-            assert dn[e] == r["done"], (s, e, "done")
+        D.assert_step(D.step(g, act), want, s, name, rew="tol", cog="tol")
     g.close()

@@ -15,11 +15,11 @@ import pytest
 import torch
 
 import _oracle
-from _fullsize_util import REW_TOL, _compare, _gpu_run, _grids, _mult, _water_positions  # noqa: F401
+from _fullsize_util import _compare, _gpu_run
+from _spawns import REF_SPAWNS, grid as _grid, hash_mult, water_positions
 
 pytestmark = pytest.mark.gpu
 
-REF_SPAWNS = [(6, 61), (10, 81), (8, 70), (11, 58), (98, 48), (98, 52), (98, 56), (96, 52)]
 
 
 def test_fullsize_config3_reference_spawns():
@@ -27,13 +27,13 @@ def test_fullsize_config3_reference_spawns():
     workload: quiet workgroups throughout), 45 steps, every env vs the oracle."""
     from lnw.batched import BatchedGame
     from lnw.config import Scenario
-    grid = _grids()[0]
+    grid = _grid(100)
     E, S, seed = 65536, 45, 1234
     sc = Scenario(landing_ops=False, auto_reset=True, episode_steps=40)
     g = BatchedGame(E, ["small"] * 4, ["large"] * 4, scenario=sc, grid=grid, seed=seed)
     g.reset(positions=REF_SPAWNS)
     acts = np.random.default_rng(5).random((S, E, 8, 4), dtype=np.float32)
-    mult = _mult(4 * 68 + 4 * 68)
+    mult = hash_mult(4 * 68 + 4 * 68)
     gpu = _gpu_run(g, acts, mult)
     assert int((g.env_state()["err"] != 0).sum()) == 0
     g.close()
@@ -49,15 +49,15 @@ def test_fullsize_config2_contact_spawns(contact):
     45 steps, every env vs the oracle."""
     from lnw.batched import BatchedGame
     from lnw.config import Scenario
-    grid = _grids()[0]
+    grid = _grid(100)
     E, S, seed = 4096, 45, 77
-    pos = _water_positions(grid, E, [(30, 45, 40, 60)] * 4 + [(55, 70, 45, 65)] * 4, seed=3)
+    pos = water_positions(grid, E, [(30, 45, 40, 60)] * 4 + [(55, 70, 45, 65)] * 4, seed=3)
     sc = Scenario(landing_ops=False, auto_reset=True, episode_steps=40)
     g = BatchedGame(E, ["small"] * 4, ["large"] * 4, scenario=sc, grid=grid, seed=seed)
     g.set_variant(contact)  # both step-kernel variants (lnw_set_variant)
     g.reset(positions=pos[0], pos_per_env=torch.from_numpy(pos))
     acts = np.random.default_rng(6).random((S, E, 8, 4), dtype=np.float32)
-    mult = _mult(4 * 68 + 4 * 68, seed=7)
+    mult = hash_mult(4 * 68 + 4 * 68, seed=7)
     gpu = _gpu_run(g, acts, mult)
     assert int((g.env_state()["err"] != 0).sum()) == 0
     g.close()
@@ -74,16 +74,16 @@ def test_fullsize_config4():
     every env vs the oracle."""
     from lnw.batched import BatchedGame
     from lnw.config import Scenario
-    grid = _grids()[1]
+    grid = _grid(200)
     E, S, seed = 8192, 42, 21
     A = 18
-    pos = _water_positions(grid, E, [(20, 60, 80, 140)] * A, seed=4)
+    pos = water_positions(grid, E, [(20, 60, 80, 140)] * A, seed=4)
     rand_ls = [0] * 16 + [1, 1]
     sc = Scenario(landing_ops=True, auto_reset=True, episode_steps=40)
     g = BatchedGame(E, ["small"] * 8, ["large"] * 8 + ["ls"] * 2, scenario=sc, grid=grid, seed=seed)
     g.reset(positions=pos[0], rand_ls=rand_ls, pos_per_env=torch.from_numpy(pos))
     acts = np.random.default_rng(8).random((S, E, A, 4), dtype=np.float32)
-    mult = _mult(8 * 84 + 10 * 92, seed=9)
+    mult = hash_mult(8 * 84 + 10 * 92, seed=9)
     gpu = _gpu_run(g, acts, mult)
     assert int((g.env_state()["err"] != 0).sum()) == 0
     g.close()

@@ -10,18 +10,10 @@ import numpy as np
 import pytest
 import torch
 
-from _oracle import load_fixture
+from _device import make_game
+from _spawns import box_positions, grid as _grid
 
 pytestmark = pytest.mark.gpu
-
-
-def _box_positions(grid, E, nb, nr, seed, box_b, box_r):
-    rng = np.random.default_rng(seed)
-    water = lambda x0, x1, y0, y1: [(x, y) for x in range(x0, x1) for y in range(y0, y1)
-                                    if grid[x, y] <= 74]
-    wb, wr = water(*box_b), water(*box_r)
-    return np.array([[wb[i] for i in rng.integers(0, len(wb), nb)] +
-                     [wr[i] for i in rng.integers(0, len(wr), nr)] for _ in range(E)], np.int32)
 
 
 CASES = {
@@ -41,24 +33,19 @@ CASES = {
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_group_kernel_equals_lane_kernel(name, monkeypatch):
     from lnw import _abi
-    from lnw.batched import BatchedGame
     from lnw.config import Scenario
     cs = CASES[name]
-    g = load_fixture("grids.npz")
-    grid = g["grid200"] if cs["G"] else g["grid100"]
+    grid = _grid(200 if cs["G"] else 100)
     E = cs["E"]
     nb, nr = len(cs["blue"]), len(cs["red"])
     A = nb + nr
     sc = Scenario(landing_ops=cs["landing_ops"], auto_reset=True, episode_steps=25,
                   trained_red=cs.get("trained_red", True))
-    pos = _box_positions(grid, E, nb, nr, 5, cs["box_b"], cs["box_r"])
+    pos = box_positions(grid, E, nb, nr, 5, cs["box_b"], cs["box_r"])
     games = []
     for no_group in (False, True):
-        if no_group:
-            monkeypatch.setenv("LNW_NO_GROUP", "1")  # read once, by lnw_create
-        gm = BatchedGame(E, cs["blue"], cs["red"], scenario=sc, grid=grid, seed=11,
-                         reward_dtype=torch.float64)
-        monkeypatch.delenv("LNW_NO_GROUP", raising=False)
+        gm = make_game(monkeypatch, E, cs["blue"], cs["red"], sc, grid, 11, reward_dtype=torch.float64,
+                       env={"LNW_NO_GROUP": "1"} if no_group else None)  # (read once, by lnw_create)
         gm.enable_analytics(eng_cap=1 << 20, ew_cap=1 << 20)
         gm.reset(positions=pos[0], pos_per_env=torch.from_numpy(pos))
         games.append(gm)
@@ -101,22 +88,19 @@ def test_group_kernel_counts_pooled_bearings(monkeypatch):
     opponent that gets a fix), which config 4's bench line reports; the
     one-lane kernel pools nothing. Results are unchanged with counters bound."""
     from lnw import _abi
-    from lnw.batched import BatchedGame
     from lnw.config import Scenario
     cs = CASES["8v10ls_g200"]
-    grid = load_fixture("grids.npz")["grid200"]
+    grid = _grid(200)
     E = cs["E"]
     nb, nr = len(cs["blue"]), len(cs["red"])
     sc = Scenario(landing_ops=True, auto_reset=True, episode_steps=25)
-    pos = _box_positions(grid, E, nb, nr, 5, cs["box_b"], cs["box_r"])
+    pos = box_positions(grid, E, nb, nr, 5, cs["box_b"], cs["box_r"])
     rng = np.random.default_rng(4)
     acts = [torch.from_numpy(rng.random((E, nb + nr, 4)).astype(np.float32)).cuda() for _ in range(12)]
     runs = {}
     for label, count, no_group in (("group", True, False), ("plain", False, False), ("lane", True, True)):
-        if no_group:
-            monkeypatch.setenv("LNW_NO_GROUP", "1")
-        gm = BatchedGame(E, cs["blue"], cs["red"], scenario=sc, grid=grid, seed=11)
-        monkeypatch.delenv("LNW_NO_GROUP", raising=False)
+        gm = make_game(monkeypatch, E, cs["blue"], cs["red"], sc, grid, 11,
+                       env={"LNW_NO_GROUP": "1"} if no_group else None)
         gm.reset(positions=pos[0], pos_per_env=torch.from_numpy(pos))
         if count:
             gm.count_work(True)

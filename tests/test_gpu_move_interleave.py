@@ -12,8 +12,8 @@ bit for bit, the ships' cells and the error flags. Needs an MI355X.
 """
 import numpy as np
 import pytest
-import torch
 
+import _device as D
 import _move_rows as M
 
 pytestmark = pytest.mark.gpu
@@ -38,55 +38,21 @@ FORMS = {
 }
 
 
-def _first(bad):
-    return np.argwhere(bad)[:4].tolist()
-
-
 @pytest.mark.parametrize("name", sorted(FORMS))
 def test_rows_vs_oracle(name, monkeypatch):
-    from lnw import _abi
-    from lnw.batched import BatchedGame
     from lnw.config import Scenario
     f = FORMS[name]
     sim = M.simulate(f["team"])
-    E, nb = f["E"], sim["nb"]
     blue, red, landing = M.TEAMS[f["team"]]
-    if f["env"]:
-        monkeypatch.setenv(f["env"], "1")  # (read by lnw_create)
     sc = Scenario(landing_ops=landing, move_mode=f["move_mode"])
-    g = BatchedGame(E, list(blue), list(red), scenario=sc, grid=M.grid(), seed=M.SEED)
-    if f["env"]:
-        monkeypatch.delenv(f["env"])
-    if f["contact"]:
-        g.set_variant(True)
-    assert g.set_epw(f["epw"]) == f["epw"]
-    g.reset(positions=M.REF_SPAWNS[:nb] + M.REF_SPAWNS[4:4 + nb], pos_per_env=torch.from_numpy(sim["pos"][:E].copy()))
-    kernel = {"team": _abi.KERNEL_TEAM, "team_contact": _abi.KERNEL_TEAM_CONTACT, "units": _abi.KERNEL_UNITS}
+    g = D.make_game(monkeypatch, f["E"], blue, red, sc, M.grid(), M.SEED, env={f["env"]: "1"} if f["env"] else None,
+                    epw=f["epw"], contact=f["contact"])  # (the knob is read by lnw_create)
+    D.start(g, sim["pos"], positions=M.ref_spawns(sim["nb"]))
     for s in range(M.STEPS):
-        act = torch.from_numpy(sim["acts"][s, :E].copy()).cuda()
-        out = {k: v.cpu().numpy() for k, v in g.step(act).items()}
-        assert g.step_kernel() == kernel[f["kernel"]], "the plan chose another kernel than the one under test"
-        after = act.cpu().numpy()
-        for k in ("obs_blue", "obs_red"):
-            bad = (out[k].view(np.int32) != sim[k][s, :E].view(np.int32)).any(axis=(1, 2))
-            assert not bad.any(), (name, s, k, "envs", _first(bad))
+        out = D.step(g, sim["acts"][s, :f["E"]], extra=("pos_after", "err"))
+        assert g.step_kernel() == D.kernel_code(f["kernel"]), "the plan chose another kernel than the one under test"
         for k in ("rew_blue", "rew_red"):
-            ref = sim[k][s, :E].astype(np.float32)
-            diff = np.abs(out[k].astype(np.float64) - ref)
+            diff = np.abs(out[k].astype(np.float64) - sim[k][s, :f["E"]].astype(np.float32))
             print(name, s, k, "max |diff| vs float32(oracle)", diff.max())
-            bad = (out[k].view(np.int32) != ref.view(np.int32)).any(axis=1)
-            assert not bad.any(), (name, s, k, "envs", _first(bad), float(diff.max()))
-        assert np.array_equal(out["done"], sim["done"][s, :E]), (name, s, "done")
-        cg, oc = out["cog"], sim["cog"][s, :E].astype(np.float32)
-        bad = ~((cg == oc) | (np.isnan(cg) & np.isnan(oc)))
-        assert not bad.any(), (name, s, "cog", _first(bad))
-        bad = (after.view(np.int32) != sim["acts_after"][s, :E].view(np.int32)).any(axis=(1, 2))
-        assert not bad.any(), (name, s, "action rows after the step", _first(bad))
-        ag = g.agents()
-        pos = np.stack([ag["x"], ag["y"]], -1)
-        bad = (pos != sim["pos_after"][s, :E]).any(axis=(1, 2))
-        assert not bad.any(), (name, s, "cells", _first(bad))
-        err = g.get(_abi.F_ERR).cpu().numpy()
-        bad = err.astype(np.uint32) != sim["err"][s, :E]
-        assert not bad.any(), (name, s, "error flags", _first(bad))
+        D.assert_step(out, sim, s, name, rew="bits", cog="exact")
     g.close()

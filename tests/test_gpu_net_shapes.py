@@ -10,12 +10,11 @@ and its LDS layout change with every n. The tolerances are the project's own
 (features rtol 1e-4 atol 2e-5, log-probabilities 1e-4, values 1e-5), applied
 against float64; every comparison prints err_hip and err_ref (the float32 host
 arm), both max-abs against float64."""
-import numpy as np
 import pytest
 import torch
 
 import _net_oracle as O
-from _oracle import load_fixture
+from _spawns import box_positions, grid as _grid
 
 pytestmark = pytest.mark.gpu
 
@@ -135,15 +134,6 @@ GAMES = {
 }
 
 
-def _box_positions(grid, E, nb, nr, seed, box_b, box_r):
-    rng = np.random.default_rng(seed)
-    water = lambda x0, x1, y0, y1: [(x, y) for x in range(x0, x1) for y in range(y0, y1)  # noqa: E731
-                                    if grid[x, y] <= 74]
-    wb, wr = water(*box_b), water(*box_r)
-    return np.array([[wb[i] for i in rng.integers(0, len(wb), nb)] +
-                     [wr[i] for i in rng.integers(0, len(wr), nr)] for _ in range(E)], np.int32)
-
-
 @pytest.mark.parametrize("name", sorted(GAMES))
 def test_fused_rollout_matches_torch_impl_large_fleets(name):
     """test_fused_rollout_matches_torch_impl (test_gpu_rollout.py) at 5 and 12
@@ -161,8 +151,8 @@ def test_fused_rollout_matches_torch_impl_large_fleets(name):
     E, T = 96, 6
     nb, nr = len(cs["blue"]), len(cs["red"])
     A = nb + nr
-    grid = load_fixture("grids.npz")["grid100"]
-    pos = torch.from_numpy(_box_positions(grid, E, nb, nr, 5, cs["box_b"], cs["box_r"]))
+    grid = _grid(100)
+    pos = torch.from_numpy(box_positions(grid, E, nb, nr, 5, cs["box_b"], cs["box_r"]))
     sc = Scenario(landing_ops=False, trained_red=red != "script", auto_reset=False)
 
     def game(**kw):

@@ -15,8 +15,7 @@ import numpy as np
 import pytest
 import torch
 
-from _oracle import load_fixture
-from test_gpu_state import _box_positions
+from _spawns import box_positions, grid as _grid
 
 pytestmark = pytest.mark.gpu
 
@@ -53,7 +52,7 @@ def _start(cs, grid):
     if cs["box"] is None:
         g.reset(positions=REF)
     else:
-        pos = _box_positions(grid, cs["E"], nb, nr, 3, cs["box"][0], cs["box"][1])
+        pos = box_positions(grid, cs["E"], nb, nr, 3, cs["box"][0], cs["box"][1])
         g.reset(positions=pos[0], pos_per_env=torch.from_numpy(pos))
     return g
 
@@ -61,7 +60,7 @@ def _start(cs, grid):
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_step_without_observation_rows(name):
     cs = CASES[name]
-    grid = load_fixture("grids.npz")["grid200" if cs["G"] else "grid100"]
+    grid = _grid(200 if cs["G"] else 100)
     E, A = cs["E"], len(cs["blue"]) + len(cs["red"])
     g1 = _start(cs, grid)
     snap = g1.get_state(device="cuda")
@@ -91,7 +90,7 @@ def test_step_without_observation_rows(name):
 def test_step_refuses_one_null_observation_pointer():
     from lnw import _abi
     cs = CASES["team_melee"]
-    g = _start(cs, load_fixture("grids.npz")["grid100"])
+    g = _start(cs, _grid(100))
     a = torch.rand((cs["E"], 8, 4), device="cuda")
     with pytest.raises(_abi.LnwError, match="both or neither"):
         _abi.check(g.L.lnw_step(g.h, a.data_ptr(), _abi.LNW_ACT_F32, None, g.obs_blue.data_ptr(), None,
@@ -102,7 +101,7 @@ def test_step_refuses_one_null_observation_pointer():
 @pytest.mark.parametrize("name", ["contact_melee", "team_melee", "group_8v10"])
 def test_observe_ex_strided_rows_and_null_side(name):
     cs = CASES[name]
-    grid = load_fixture("grids.npz")["grid200" if cs["G"] else "grid100"]
+    grid = _grid(200 if cs["G"] else 100)
     E, A = cs["E"], len(cs["blue"]) + len(cs["red"])
     g1 = _start(cs, grid)
     rng = np.random.default_rng(8)

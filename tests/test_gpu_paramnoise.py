@@ -395,6 +395,7 @@ def test_reference_rollout_with_noised_actors(impl):
     observations, rewards, values and log-probabilities as
     tests/test_gpu_rollout_golden.py checks them."""
     from _oracle import load_fixture
+    from _spawns import grid as _grid
     from lnw.batched import BatchedGame
     from lnw.config import Scenario
     from lnw.ppolearn import actor_slices
@@ -403,7 +404,7 @@ def test_reference_rollout_with_noised_actors(impl):
     meta = json.loads(str(fx["meta"]))
     eps, R, T, nb = meta["episodes"], meta["R"], meta["T"], meta["nb"]
     types = eps[0]["types"]
-    grid = load_fixture("grids.npz")["grid100"]
+    grid = _grid(100)
     sc = Scenario(landing_ops=False, trained_red=False, tactics="aggressive", side="blue", auto_reset=False)
     g = BatchedGame(R, [NAMES[t] for t in types[:nb]], [NAMES[t] for t in types[nb:]], scenario=sc, grid=grid,
                     reward_dtype=torch.float64)

@@ -13,19 +13,19 @@ import numpy as np
 import pytest
 import torch
 
+from _device import REW_TOL
 from _oracle import (GOLDEN, OracleEnv, astar_batch, episode_meta, load_fixture, los_batch,
                      move_batch)
+from _spawns import REF_SPAWNS, box_positions, grids as _grids
 
 pytestmark = pytest.mark.gpu
 
 EPISODES = sorted(os.path.basename(p) for p in glob.glob(os.path.join(GOLDEN, "ep_*.npz")))
-REW_TOL = 1e-5
 
 
 @pytest.fixture(scope="module")
 def grids():
-    g = load_fixture("grids.npz")
-    return [g["grid100"], g["grid200"]]
+    return list(_grids())
 
 
 @pytest.fixture(scope="module")
@@ -437,15 +437,6 @@ def test_shard_invariance(grids):
         g.close()
 
 
-def _melee_positions(grid, E, nb, nr, seed, box_b=(30, 45, 40, 60), box_r=(55, 70, 45, 65)):
-    rng = np.random.default_rng(seed)
-    water = lambda x0, x1, y0, y1: [(x, y) for x in range(x0, x1) for y in range(y0, y1)
-                                    if grid[x, y] <= 74]
-    wb, wr = water(*box_b), water(*box_r)
-    return np.array([[wb[i] for i in rng.integers(0, len(wb), nb)] +
-                     [wr[i] for i in rng.integers(0, len(wr), nr)] for _ in range(E)], np.int32)
-
-
 @pytest.mark.parametrize("epw,contact", [(64, False), (16, False), (1, False), (64, True), (16, True)])
 def test_philox_4v4_vs_oracle_launch_shapes(grids, epw, contact):
     """4v4 split spawns (fire, EW bearings and fixes happen) in production
@@ -461,7 +452,7 @@ def test_philox_4v4_vs_oracle_launch_shapes(grids, epw, contact):
                     grid=grid, seed=11)
     assert g.set_epw(epw) == epw
     g.set_variant(contact)
-    pos = _melee_positions(grid, E, 4, 4, seed=epw)
+    pos = box_positions(grid, E, 4, 4, seed=epw)
     g.reset(positions=pos[0], pos_per_env=torch.from_numpy(pos))
     oracles = []
     for e in range(E):
@@ -497,7 +488,7 @@ def test_contact_pooled_bearings(grids):
     from lnw.config import Scenario
     grid = grids[0]
     E, S = 1024, 6
-    pos = _melee_positions(grid, E, 4, 4, seed=5)
+    pos = box_positions(grid, E, 4, 4, seed=5)
     rng = np.random.default_rng(7)
     acts = [rng.random((E, 8, 4)).astype(np.float32) for _ in range(S)]
     outs = []
@@ -562,7 +553,6 @@ def test_config4_launch_shape_invariance(grids):
         g.close()
 
 
-REF_SPAWNS = [(6, 61), (10, 81), (8, 70), (11, 58), (98, 48), (98, 52), (98, 56), (96, 52)]
 
 
 @pytest.mark.parametrize("trained_red", [True, False])
@@ -583,7 +573,7 @@ def test_quiet_path_vs_oracle(grids, trained_red):
                     grid=grid, seed=21)
     assert g.set_epw(64) == 64
     pos = np.array([REF_SPAWNS] * E, np.int32)
-    pos[96:] = _melee_positions(grid, 32, 4, 4, seed=4)
+    pos[96:] = box_positions(grid, 32, 4, 4, seed=4)
     g.reset(positions=pos[0], pos_per_env=torch.from_numpy(pos))
     oracles = []
     for e in range(E):
@@ -632,7 +622,7 @@ def test_quiet_path_vs_phase_s_long(grids, spawns, trained_red, E, monkeypatch):
     if spawns == "mixed":
         for w in range(1, (E + 63) // 64, 2):
             n = min(64, E - 64 * w)
-            pos[64 * w:64 * w + n] = _melee_positions(grids[0], n, 4, 4, seed=w)
+            pos[64 * w:64 * w + n] = box_positions(grids[0], n, 4, 4, seed=w)
     games = []
     for epw, skip in ((64, None), (16, None), (8, None), (64, "512")):
         if skip:
@@ -681,8 +671,8 @@ def test_philox_long_sensor_ranges_vs_oracle(grids, duct):
     g = BatchedGame(E, ["small"] * 4, ["large"] * 4, scenario=Scenario(landing_ops=False),
                     grid=grid, seed=5)
     assert g.set_epw(64) == 64
-    pos = _melee_positions(grid, E, 4, 4, seed=int(duct * 10), box_b=(20, 35, 35, 65),
-                           box_r=(60, 75, 35, 65))
+    pos = box_positions(grid, E, 4, 4, seed=int(duct * 10), box_b=(20, 35, 35, 65),
+                        box_r=(60, 75, 35, 65))
     g.reset(positions=pos[0], pos_per_env=torch.from_numpy(pos))
     g.set(F_DUCT, torch.full((E,), duct, dtype=torch.float64))
     oracles = []
@@ -729,7 +719,7 @@ def test_quiet_path_dtypes_vs_oracle(grids, mode, trained_red):
                     grid=grid, seed=31)
     assert g.set_epw(64) == 64
     pos = np.array([REF_SPAWNS] * E, np.int32)
-    pos[96:] = _melee_positions(grid, 32, 4, 4, seed=6)
+    pos[96:] = box_positions(grid, 32, 4, 4, seed=6)
     g.reset(positions=pos[0], pos_per_env=torch.from_numpy(pos))
     oracles = []
     for e in range(E):

@@ -15,19 +15,18 @@ import numpy as np
 import pytest
 import torch
 
+import _device as D
 import _quiet_cases as Q
+from _spawns import grid, ref_spawns
 
 pytestmark = pytest.mark.gpu
 
-REW_TOL = 1e-5  # the suite's reward tolerance (float32 outputs of float64 sums below 1 000)
 FORMS = sorted(Q.FORMS)
 
 
 def _make(name, monkeypatch, E, *, auto_reset=False, trained_red=True, prof=False, seed=0):
     """A handle in the row's form. The knobs are read by lnw_create and
-    LNW_EPW_RT by the constructor's automatic epw choice: set around it."""
-    from lnw import _abi
-    from lnw.batched import BatchedGame
+    LNW_EPW_RT by the constructor's automatic epw choice."""
     from lnw.config import Scenario
     f = Q.FORMS[name]
     nb = f["nb"]
@@ -36,63 +35,24 @@ def _make(name, monkeypatch, E, *, auto_reset=False, trained_red=True, prof=Fals
         env["LNW_PROF"] = "1"
     if f.get("epw_rt"):
         env["LNW_EPW_RT"] = str(f["epw"])
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
     sc = Scenario(landing_ops=f["red"] is not None, auto_reset=auto_reset, episode_steps=40,
                   trained_red=trained_red)
-    g = BatchedGame(E, ["large"] * nb, list(f["red"] or ["large"] * nb), scenario=sc, grid=Q._grid(f["G"]),
-                    seed=seed)
-    for k in env:
-        monkeypatch.delenv(k, raising=False)
+    g = D.make_game(monkeypatch, E, ["large"] * nb, f["red"] or ["large"] * nb, sc, grid(f["G"]), seed, env=env,
+                    contact=f["contact"])
     if f.get("epw_rt"):
         assert g.epw == f["epw"]
-    if f["contact"]:
-        g.set_variant(True)
     assert g.set_epw(f["epw"]) == f["epw"] and g.epw == f["epw"]
-    kernel = {"team": _abi.KERNEL_TEAM, "team_contact": _abi.KERNEL_TEAM_CONTACT, "units": _abi.KERNEL_UNITS}
-    return g, kernel[f["kernel"]]
-
-
-def _start(g, sim, seed):
-    from lnw._abi import F_DUCT
-    nb = g.nb
-    g.set_rng(seed)
-    g.reset(positions=Q.REF_SPAWNS[:nb] + Q.REF_SPAWNS[4:4 + nb], pos_per_env=torch.from_numpy(sim["pos"]))
-    duct = g.get(F_DUCT).cpu().numpy()
-    probes = sim["probes"]
-    duct[probes] = sim["duct"][probes]
-    g.set(F_DUCT, torch.from_numpy(duct))
-
-
-def _first(bad):
-    return np.argwhere(bad)[:4].tolist()
+    return g, D.kernel_code(f["kernel"])
 
 
 def _compare(g, sim, steps, tag):
     """Step the device over the layout's actions; every env and step against
     the oracle's record."""
-    from lnw._abi import F_RNG
     for s in range(steps):
-        act = torch.from_numpy(sim["acts"][s]).cuda()
-        out = {k: v.cpu().numpy() for k, v in g.step(act).items()}
-        after = act.cpu().numpy()
-        for k in ("obs_blue", "obs_red"):  # bit for bit
-            bad = (out[k].view(np.int32) != sim[k][s].view(np.int32)).any(axis=(1, 2))
-            assert not bad.any(), (tag, s, k, "envs", _first(bad))
-        for k in ("rew_blue", "rew_red"):
-            bad = (np.abs(out[k] - sim[k][s]) > REW_TOL).any(axis=1)
-            assert not bad.any(), (tag, s, k, "envs", _first(bad))
-        assert np.array_equal(out["done"], sim["done"][s]), (tag, s, "done", _first(out["done"] != sim["done"][s]))
-        cg, oc = out["cog"], sim["cog"][s]
-        bad = ~((np.abs(cg - oc) <= 1e-5) | (np.isnan(cg) & np.isnan(oc)))
-        assert not bad.any(), (tag, s, "cog", _first(bad))
-        bad = (after.view(np.int32) != sim["acts_after"][s].view(np.int32)).any(axis=(1, 2))
-        assert not bad.any(), (tag, s, "action rows after the step", _first(bad))
         # the env's draw counter: a step wrongly taken as quiet skips the bearings'
         # draws, which with a single bearing (no fix, no target) leave no other
         # trace before the next reset draws its ducting
-        bad = g.get(F_RNG).cpu().numpy() != sim["ctr"][s]
-        assert not bad.any(), (tag, s, "draw counter", _first(bad))
+        D.assert_step(D.step(g, sim["acts"][s], extra=("ctr",)), sim, s, tag, rew="tol", cog="tol")
 
 
 @pytest.mark.parametrize("name", FORMS)
@@ -106,7 +66,7 @@ def test_reach(name, monkeypatch):
     quiet_wgs = loud_wgs = 0
     for seed in Q.REACH_SEEDS:
         sim = Q.form_sim(name, seed)
-        _start(g, sim, seed)
+        D.start(g, sim["pos"], seed=seed, duct=sim["duct"], positions=ref_spawns(g.nb))
         _compare(g, sim, Q.REACH_STEPS, (name, seed))
         assert g.step_kernel() == kernel
         assert not g.env_state()["err"].any() and not sim["err"].any()
@@ -127,7 +87,7 @@ def test_forms_45_steps(name, trained_red, monkeypatch):
     seed = Q.REACH_SEEDS[0]
     sim = Q.form_sim(name, seed, steps=45, trained_red=trained_red, horizon=40)
     g, kernel = _make(name, monkeypatch, sim["E"], auto_reset=True, trained_red=trained_red)
-    _start(g, sim, seed)
+    D.start(g, sim["pos"], seed=seed, duct=sim["duct"], positions=ref_spawns(g.nb))
     _compare(g, sim, 45, (name, trained_red))
     assert g.step_kernel() == kernel
     # the 40th step ends every episode no victory ended before: done stays 1
@@ -150,7 +110,7 @@ def test_form_ran(name, monkeypatch, capfd):
     nb, epw = f["nb"], f["epw"]
     E = Q.form_sim(name, Q.REACH_SEEDS[0])["E"]
     g, kernel = _make(name, monkeypatch, E, prof=True, seed=3)
-    g.reset(positions=Q.REF_SPAWNS[:nb] + Q.REF_SPAWNS[4:4 + nb])
+    g.reset(positions=ref_spawns(nb))
     capfd.readouterr()
     g.step(torch.from_numpy(np.random.default_rng(1).random((E, 2 * nb, 4), dtype=np.float32)).cuda())
     torch.cuda.synchronize()
@@ -174,7 +134,7 @@ def test_every_epw_is_accepted():
     from lnw import _abi
     from lnw.batched import BatchedGame
     from lnw.config import Scenario
-    g = BatchedGame(40, ["large"] * 4, ["large"] * 4, scenario=Scenario(landing_ops=False), grid=Q._grid(100))
+    g = BatchedGame(40, ["large"] * 4, ["large"] * 4, scenario=Scenario(landing_ops=False), grid=grid(100))
     for epw in range(1, 65):
         assert g.set_epw(epw) == epw
     for epw in (-1, 65, 128):

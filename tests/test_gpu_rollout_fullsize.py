@@ -18,18 +18,10 @@ import pytest
 import torch
 
 import _oracle
+from _spawns import REF_SPAWNS, grid as _grid, melee_block
 
 pytestmark = pytest.mark.gpu
 
-REF_SPAWNS = [(6, 61), (10, 81), (8, 70), (11, 58), (98, 48), (98, 52), (98, 56), (96, 52)]
-
-
-def _melee(grid, n, seed):
-    rng = np.random.default_rng(seed)
-    wb = np.argwhere(grid[30:45, 40:60] <= 74) + np.array([30, 40])
-    wr = np.argwhere(grid[55:70, 45:65] <= 74) + np.array([55, 45])
-    return np.concatenate([wb[rng.integers(0, len(wb), (n, 4))], wr[rng.integers(0, len(wr), (n, 4))]],
-                          1).astype(np.int32)
 
 
 @pytest.mark.parametrize("strided", [False, True])
@@ -39,12 +31,12 @@ def test_rollout_env_side_vs_oracle(layout, strided, monkeypatch):
     from lnw.batched import BatchedGame
     from lnw.config import Scenario
     monkeypatch.setattr(R, "STRIDED_POLICY_INPUT", strided)
-    grid = _oracle.load_fixture("grids.npz")["grid100"]
+    grid = _grid(100)
     E, T, seed, nb = 32768, 40, 77, 4
     pos = np.array([REF_SPAWNS] * E, np.int32)
     if layout == "mixed":  # melee spawns in every other 64-env block: contact from step 0
         blocks = np.arange(E).reshape(-1, 128)[:, 64:].reshape(-1)
-        pos[blocks] = _melee(grid, len(blocks), seed=5)
+        pos[blocks] = melee_block(grid, len(blocks), seed=5)
     # bench.mappo_rollout's scenario, actor, critic and sampling
     sc = Scenario(landing_ops=False, tactics="aggressive", side="blue", trained_red=False,
                   auto_reset=True, episode_steps=40)

@@ -25,6 +25,7 @@ import pytest
 import torch
 
 from _oracle import GOLDEN, load_fixture
+from _spawns import grid as _grid
 
 pytestmark = pytest.mark.gpu
 
@@ -62,7 +63,7 @@ def _rollout_case(name, impl, contact=False):
     eps, R, T, nb = meta["episodes"], meta["R"], meta["T"], meta["nb"]
     types = eps[0]["types"]
     A = len(types)
-    grid = load_fixture("grids.npz")["grid100"]
+    grid = _grid(100)
     sc = Scenario(landing_ops=meta["landing_ops"], trained_red=meta["trained_red"],
                   tactics="aggressive", side="blue", auto_reset=False)
     g = BatchedGame(R, [NAMES[t] for t in types[:nb]], [NAMES[t] for t in types[nb:]],

@@ -10,18 +10,11 @@ import pytest
 import torch
 
 import _oracle
+from _fullsize_util import _compare
+from _spawns import REF_SPAWNS, grid as _grid, hash_mult, melee_block
 
 pytestmark = pytest.mark.gpu
 
-REF_SPAWNS = [(6, 61), (10, 81), (8, 70), (11, 58), (98, 48), (98, 52), (98, 56), (96, 52)]
-
-
-def _melee(grid, n, seed, nb=4, nr=4):
-    rng = np.random.default_rng(seed)
-    wb = np.argwhere(grid[30:45, 40:60] <= 74) + np.array([30, 40])
-    wr = np.argwhere(grid[55:70, 45:65] <= 74) + np.array([55, 45])
-    return np.concatenate([wb[rng.integers(0, len(wb), (n, nb))], wr[rng.integers(0, len(wr), (n, nr))]],
-                          1).astype(np.int32)
 
 
 CASES = {
@@ -45,7 +38,7 @@ def _setup(cs, grid, seed):
     pos = np.array([spawns] * E, np.int32)
     blk = cs["block"]
     loud = np.array([e for e in range(E) if (e // blk) % 2 == 1])  # every other workgroup fights
-    pos[loud] = _melee(grid, len(loud), seed=E + nb, nb=nb, nr=nb)
+    pos[loud] = melee_block(grid, len(loud), seed=E + nb, nb=nb, nr=nb)
     sc = Scenario(landing_ops=False, auto_reset=True, episode_steps=40, trained_red=cs["trained_red"])
     g = BatchedGame(E, ["small"] * nb, ["large"] * nb, scenario=sc, grid=grid, seed=seed)
     if cs["epw"]:
@@ -67,7 +60,7 @@ def _same(x, y):
 def test_step_seq_equals_steps(name):
     from lnw import _abi
     cs = CASES[name]
-    grid = _oracle.load_fixture("grids.npz")["grid100"]
+    grid = _grid(100)
     E, nb, K = cs["E"], cs["nb"], 45
     A = 2 * nb
     acts = torch.from_numpy(np.random.default_rng(21).random((K, E, A, 4), dtype=np.float32)).cuda()
@@ -111,17 +104,17 @@ def test_step_seq_vs_oracle_shard():
     cog (orc_fullsize_range)."""
     from lnw.batched import BatchedGame
     from lnw.config import Scenario
-    grid = _oracle.load_fixture("grids.npz")["grid100"]
+    grid = _grid(100)
     E, S, seed = 8192, 45, 313
     pos = np.array([REF_SPAWNS] * E, np.int32)
     loud = np.arange(E).reshape(-1, 32)[:, 16:].reshape(-1)
-    pos[loud] = _melee(grid, len(loud), seed=7)
+    pos[loud] = melee_block(grid, len(loud), seed=7)
     sc = Scenario(landing_ops=False, auto_reset=True, episode_steps=40)
     g = BatchedGame(E, ["small"] * 4, ["large"] * 4, scenario=sc, grid=grid, seed=seed)
     g.reset(positions=REF_SPAWNS, pos_per_env=torch.from_numpy(pos))
     acts = np.random.default_rng(9).random((S, E, 8, 4), dtype=np.float32)
     out = g.step_seq(torch.from_numpy(acts).cuda(), keep="all")
-    mult = (np.random.default_rng(4).integers(0, 1 << 30, 2 * 4 * 68, dtype=np.int64) * 2 + 1)
+    mult = hash_mult(2 * 4 * 68, seed=4)
     mt = torch.from_numpy(mult).cuda()
     w = torch.cat([out["obs_blue"].reshape(S, E, -1), out["obs_red"].reshape(S, E, -1)], 2)
     w = w.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
@@ -131,11 +124,7 @@ def test_step_seq_vs_oracle_shard():
     assert int((g.env_state()["err"] != 0).sum()) == 0
     g.close()
     oh, orw, od, oc = _oracle.fullsize(grid, 4, 4, [0] * 4 + [1] * 4, pos, acts, mult, seed, 40, pos_per_env=True)
-    bad = np.argwhere(gh != oh)
-    assert bad.size == 0, f"{len(bad)} (step, env) hashes differ, first {bad[:6].tolist()}"
-    assert np.array_equal(gd, od)
-    assert np.allclose(gr, orw, rtol=0, atol=1e-5)
-    assert np.allclose(gc, oc, rtol=0, atol=1e-5, equal_nan=True)
+    _compare((gh, gr, gd, gc), (oh, orw, od, oc), "shard8192")
     assert (gd == 0).any()
 
 
@@ -144,13 +133,13 @@ def test_step_seq_obs_false_keep_all():
     other outputs equal K step(obs=False) calls."""
     from lnw.batched import BatchedGame
     from lnw.config import Scenario
-    grid = _oracle.load_fixture("grids.npz")["grid100"]
+    grid = _grid(100)
     E, K = 256, 6
     acts = torch.from_numpy(np.random.default_rng(3).random((K, E, 8, 4), dtype=np.float32)).cuda()
     outs = []
     for mode in ("steps", "seq"):
         g = BatchedGame(E, ["small"] * 4, ["large"] * 4, scenario=Scenario(landing_ops=False), grid=grid, seed=9)
-        g.reset(positions=REF_SPAWNS, pos_per_env=torch.from_numpy(_melee(grid, E, seed=4)))
+        g.reset(positions=REF_SPAWNS, pos_per_env=torch.from_numpy(melee_block(grid, E, seed=4)))
         if mode == "steps":
             outs.append([{k: v.clone() for k, v in g.step(acts[k].clone(), obs=False).items()
                           if not k.startswith("obs_")} for k in range(K)])

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from _oracle import load_fixture
+from _spawns import REF_SPAWNS, box_positions, grid as _grid
 
 pytestmark = pytest.mark.gpu
 
@@ -28,15 +28,6 @@ CASES = {
                       trained_red=True, box_b=(30, 45, 40, 60), box_r=(50, 65, 45, 65), E=192,
                       dtype=torch.float32),
 }
-
-
-def _box_positions(grid, E, nb, nr, seed, box_b, box_r):
-    rng = np.random.default_rng(seed)
-    water = lambda x0, x1, y0, y1: [(x, y) for x in range(x0, x1) for y in range(y0, y1)  # noqa: E731
-                                    if grid[x, y] <= 74]
-    wb, wr = water(*box_b), water(*box_r)
-    return np.array([[wb[i] for i in rng.integers(0, len(wb), nb)] +
-                     [wr[i] for i in rng.integers(0, len(wr), nr)] for _ in range(E)], np.int32)
 
 
 def _game(cs, grid, seed):
@@ -67,11 +58,11 @@ def _same(t1, t2):
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_snapshot_restore_continues_identically(name):
     cs = CASES[name]
-    grid = load_fixture("grids.npz")["grid200" if cs["G"] else "grid100"]
+    grid = _grid(200 if cs["G"] else 100)
     E = cs["E"]
     nb, nr = len(cs["blue"]), len(cs["red"])
     A = nb + nr
-    pos = _box_positions(grid, E, nb, nr, 3, cs["box_b"], cs["box_r"])
+    pos = box_positions(grid, E, nb, nr, 3, cs["box_b"], cs["box_r"])
     rng = np.random.default_rng(9)
     acts = [torch.from_numpy(rng.random((E, A, 4))).to(cs["dtype"]).cuda() for _ in range(30)]
     g = _game(cs, grid, seed=5)
@@ -99,15 +90,14 @@ def test_snapshot_restore_continues_identically(name):
 
 def test_snapshot_refuses_other_shapes_and_terrain():
     from lnw import _abi
-    grids = load_fixture("grids.npz")
     cs = CASES["4v4"]
-    g = _game(cs, grids["grid100"], seed=1)
-    g.reset(positions=[(6, 61), (10, 81), (8, 70), (11, 58), (98, 48), (98, 52), (98, 56), (96, 52)])
+    g = _game(cs, _grid(100), seed=1)
+    g.reset(positions=REF_SPAWNS)
     snap = g.get_state()
-    other = _game(dict(cs, E=128), grids["grid100"], seed=1)
+    other = _game(dict(cs, E=128), _grid(100), seed=1)
     with pytest.raises(_abi.LnwError, match="shape"):
         other.set_state(snap)
-    terrain = grids["grid100"].copy()
+    terrain = _grid(100).copy()
     terrain[0, 0] ^= 1
     moved = _game(cs, terrain, seed=1)
     with pytest.raises(_abi.LnwError, match="terrain"):
@@ -117,7 +107,7 @@ def test_snapshot_refuses_other_shapes_and_terrain():
     with pytest.raises(_abi.LnwError, match="magic"):
         g.set_state(bad)
     # another fleet of the same shape: its rows would not fit this game's buffers
-    med = _game(dict(cs, blue=["medium"] * 4), grids["grid100"], seed=1)
+    med = _game(dict(cs, blue=["medium"] * 4), _grid(100), seed=1)
     with pytest.raises(ValueError, match="fleet"):
         med.set_state(snap)
     # a snapshot whose side mixes medium and speed-3 ships is refused by the

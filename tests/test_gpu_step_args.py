@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 import torch
 
-from _oracle import load_fixture
+from _spawns import grid as _grid
 
 pytestmark = pytest.mark.gpu
 
@@ -26,10 +26,6 @@ BOX_B, BOX_R = (30, 45, 40, 60), (55, 70, 45, 65)  # contact spawns (fire, EW fi
 
 # (E, environments per workgroup: 0 = automatic)
 SHAPES = {"units_256": (256, 64), "direct_64": (64, 16), "partial_40": (40, 0)}
-
-
-def _grid():
-    return load_fixture("grids.npz")["grid100"]
 
 
 def _positions(grid, E, seed=3):

@@ -11,7 +11,8 @@ import numpy as np
 import pytest
 import torch
 
-from _oracle import load_fixture
+import _device as D
+from _spawns import grid as _grid
 
 pytestmark = pytest.mark.gpu
 
@@ -42,26 +43,17 @@ def _positions(grid, nb, nr):
 
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_step_plan(name, monkeypatch):
-    from lnw import _abi
-    from lnw.batched import BatchedGame
     from lnw.config import Scenario
     blue, red, knobs, contact, los_mode, E, epw, kernel, auto_epw = CASES[name]
-    grid = load_fixture("grids.npz")["grid100"]
-    for k in knobs:
-        monkeypatch.setenv(k, "1")  # read once, by lnw_create
-    g = BatchedGame(E, blue, red, scenario=Scenario(landing_ops=False, los_mode=los_mode), grid=grid, seed=3)
-    for k in knobs:
-        monkeypatch.delenv(k)
-    if contact:
-        g.set_variant(True)
-    if epw is not None:
-        assert g.set_epw(epw) == epw
+    grid = _grid(100)
+    g = D.make_game(monkeypatch, E, blue, red, Scenario(landing_ops=False, los_mode=los_mode), grid, 3,
+                    env=dict.fromkeys(knobs, "1"), epw=epw, contact=contact)  # (knobs: read once, by lnw_create)
     g.reset(positions=_positions(grid, len(blue), len(red)))
     act = torch.from_numpy(np.random.default_rng(1).random((E, len(blue) + len(red), 4), dtype=np.float32)).cuda()
     g.step(act)
     torch.cuda.synchronize()
     print(name, "kernel", g.step_kernel(), "epw", g.epw)
-    assert g.step_kernel() == getattr(_abi, "KERNEL_" + kernel)
+    assert g.step_kernel() == D.kernel_code(kernel)
     if epw is None:
         assert g.epw == auto_epw
     assert int((g.env_state()["err"] != 0).sum()) == 0

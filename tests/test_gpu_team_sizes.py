@@ -27,10 +27,12 @@ import numpy as np
 import pytest
 import torch
 
+import _device as D
 import _fix_order_cases as F
 import _oracle
 import _team_cases as T
 from _fullsize_util import _compare, _gpu_run
+from _spawns import grid as _grid
 
 pytestmark = pytest.mark.gpu
 
@@ -45,35 +47,28 @@ WANTED = {("group", T.ALL), ("group", "ms tls dlz"), ("group", "ms tls"), ("grou
 def _game(cs, monkeypatch, E, prof=False):
     """A handle of the case's shape (LNW_NO_GROUP and LNW_PROF are read once, by
     lnw_create: set around it), reset to the case's spawns."""
-    from lnw.batched import BatchedGame
     from lnw.config import Scenario
     env = {}
     if cs["no_group"]:
         env["LNW_NO_GROUP"] = "1"
     if prof:
         env["LNW_PROF"] = "1"
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
     sc = Scenario(landing_ops=cs["landing_ops"], auto_reset=True, episode_steps=T.HORIZON,
                   trained_red=cs["trained_red"])
-    g = BatchedGame(E, cs["blue"], cs["red"], scenario=sc, grid=T.grid(cs), seed=T.SEED)
-    for k in env:
-        monkeypatch.delenv(k, raising=False)
-    pos = T.positions(cs)[:E]
-    g.reset(positions=pos[0], pos_per_env=torch.from_numpy(pos))
+    g = D.make_game(monkeypatch, E, cs["blue"], cs["red"], sc, T.grid(cs), T.SEED, env=env)
+    D.start(g, T.positions(cs))
     return g
 
 
 def _form_ran(cs, monkeypatch, capfd):
     """(kernel, LDS form) of one step of a 33-env handle of the case's shape under LNW_PROF."""
-    from lnw import _abi
     g = _game(cs, monkeypatch, 33, prof=True)
     capfd.readouterr()
     act = torch.from_numpy(T.actions(cs)[0, :33]).cuda()
     g.step(act)
     torch.cuda.synchronize()
     err = capfd.readouterr().err
-    kernel = {_abi.KERNEL_GROUP: "group", _abi.KERNEL_GENERIC: "generic"}.get(g.step_kernel(), g.step_kernel())
+    kernel = next((k for k in ("group", "generic") if g.step_kernel() == D.kernel_code(k)), g.step_kernel())
     g.close()
     m = LDS_LINE.search(err)
     if kernel != "group":
@@ -87,7 +82,6 @@ def _form_ran(cs, monkeypatch, capfd):
 
 @pytest.mark.parametrize("name", NAMES)
 def test_case_matches_oracle(name, monkeypatch, capfd):
-    from lnw import _abi
     cs = T.CASES[name]
     ran = _form_ran(cs, monkeypatch, capfd)
     assert ran == (cs["kernel"], cs["form"]), (name, ran)
@@ -95,7 +89,7 @@ def test_case_matches_oracle(name, monkeypatch, capfd):
     acts = T.actions(cs)
     g = _game(cs, monkeypatch, cs["E"])
     gpu = _gpu_run(g, acts, T.mult(cs), after=True)
-    assert g.step_kernel() == (_abi.KERNEL_GROUP if cs["kernel"] == "group" else _abi.KERNEL_GENERIC)
+    assert g.step_kernel() == D.kernel_code(cs["kernel"])
     err = g.env_state()["err"]
     g.close()
     _compare(gpu[:4], (orc["hash"], orc["rew"], orc["done"], orc["cog"]), name)
@@ -163,29 +157,23 @@ def test_fix_mean_sums_in_numpy_order(name, no_group, monkeypatch):
     the group kernel, FixAcc of the one-lane kernel). 33 envs on the same
     tape: observations bit for bit, rewards, target-list counts, the tape
     position and the error flags against the oracle's step."""
-    from lnw import _abi
-    from lnw.batched import BatchedGame
     from lnw.config import Scenario
     c = F.CASES[name]
     n, E = len(c["blue"]), 33
     r, o = F.oracle_step(c)
-    if no_group:
-        monkeypatch.setenv("LNW_NO_GROUP", "1")
-    g = BatchedGame(E, ["small"] * n, ["large"], scenario=Scenario(landing_ops=False),
-                    grid=_oracle.load_fixture("grids.npz")["grid100"])
-    monkeypatch.delenv("LNW_NO_GROUP", raising=False)
+    g = D.make_game(monkeypatch, E, ["small"] * n, ["large"], Scenario(landing_ops=False), _grid(100),
+                    env={"LNW_NO_GROUP": "1"} if no_group else None)
     tape = F.tape(c)
-    g.set_tape(np.tile(tape, E), np.arange(E + 1, dtype=np.int64) * len(tape))
-    pos = np.tile(F.positions(c), (E, 1, 1))
-    g.reset(positions=pos[0], pos_per_env=torch.from_numpy(pos))
+    D.start(g, np.tile(F.positions(c), (E, 1, 1)),
+            tape=(np.tile(tape, E), np.arange(E + 1, dtype=np.int64) * len(tape)))
     out = {k: v.cpu().numpy() for k, v in g.step(torch.zeros((E, n + 1, 4), dtype=torch.float32).cuda()).items()}
-    assert g.step_kernel() == (_abi.KERNEL_GENERIC if no_group else _abi.KERNEL_GROUP)
+    assert g.step_kernel() == D.kernel_code("generic" if no_group else "group")
     es, cnt = g.env_state(), g.agents()["tl_cnt"]
     g.close()
     assert (cnt == np.array([c["want"]] * n + [0])).all(), cnt[:2]
     for k in ("obs_blue", "obs_red"):
         assert (out[k].view(np.int32) == r[k].astype(np.float32).view(np.int32)).all(), k
-    assert np.abs(out["rew_blue"] - r["rew_blue"]).max() <= 1e-5 and np.abs(out["rew_red"] - r["rew_red"]).max() <= 1e-5
+    assert all(np.abs(out[k] - r[k]).max() <= D.REW_TOL for k in ("rew_blue", "rew_red"))
     ost = o.env_state()
     assert (es["rng"] == ost["tape_pos"]).all() and (es["err"] == ost["err"]).all() and ost["err"] == 0
 
@@ -206,7 +194,7 @@ def test_size_limit(nb, nr, G, loads):
     from lnw import _abi
     from lnw.config import Scenario
     L = _abi.load()
-    grid = np.ascontiguousarray(T._grids()[0 if G == 100 else 1], np.uint8)
+    grid = np.ascontiguousarray(_grid(G), np.uint8)
     p = Scenario(landing_ops=False).params()
     h = C.c_void_p()
     _abi.check(L.lnw_create(C.byref(p), 40, nb, nr, 0, 0, C.byref(h)))

@@ -18,25 +18,13 @@ import pytest
 import torch
 
 import _oracle
+from _fullsize_util import _compare, _gpu_run
+from _spawns import REF_SPAWNS, grid as _grid, hash_mult, melee_block
 
 pytestmark = pytest.mark.gpu
 
-REW_TOL = 1e-5
-REF_SPAWNS = [(6, 61), (10, 81), (8, 70), (11, 58), (98, 48), (98, 52), (98, 56), (96, 52)]
 # unit kinds per workgroup (E = 512: two workgroups of four 64-env units)
 LAYOUT = [["ref", "melee", "ref", "mixed"], ["melee", "ref", "mixed", "ref"]]
-
-
-def _mult(n, seed=99):
-    return (np.random.default_rng(seed).integers(0, 1 << 30, n, dtype=np.int64) * 2 + 1)
-
-
-def _melee(grid, n, seed):
-    rng = np.random.default_rng(seed)
-    wb = np.argwhere(grid[30:45, 40:60] <= 74) + np.array([30, 40])
-    wr = np.argwhere(grid[55:70, 45:65] <= 74) + np.array([55, 45])
-    return np.concatenate([wb[rng.integers(0, len(wb), (n, 4))], wr[rng.integers(0, len(wr), (n, 4))]],
-                          1).astype(np.int32)
 
 
 def _positions(grid):
@@ -45,9 +33,9 @@ def _positions(grid):
         for u, kind in enumerate(kinds):
             e0 = 256 * w + 64 * u
             if kind == "melee":
-                pos[e0:e0 + 64] = _melee(grid, 64, seed=e0)
+                pos[e0:e0 + 64] = melee_block(grid, 64, seed=e0)
             elif kind == "mixed":
-                pos[e0 + 32:e0 + 64] = _melee(grid, 32, seed=e0)
+                pos[e0 + 32:e0 + 64] = melee_block(grid, 32, seed=e0)
     return pos
 
 
@@ -56,7 +44,7 @@ def test_units_kernel_vs_oracle(trained_red):
     from lnw import _abi
     from lnw.batched import BatchedGame
     from lnw.config import Scenario
-    grid = _oracle.load_fixture("grids.npz")["grid100"]
+    grid = _grid(100)
     E, S, seed = 512, 45, 4242
     pos = _positions(grid)
     sc = Scenario(landing_ops=False, auto_reset=True, episode_steps=40, trained_red=trained_red)
@@ -64,33 +52,16 @@ def test_units_kernel_vs_oracle(trained_red):
     assert g.set_epw(64) == 64
     g.reset(positions=REF_SPAWNS, pos_per_env=torch.from_numpy(pos))
     acts = np.random.default_rng(12 + trained_red).random((S, E, 8, 4), dtype=np.float32)
-    mult = _mult(2 * 4 * 68, seed=5)
-    mt = torch.from_numpy(mult).cuda()
-    hs, rews, dones, cogs, after = [], [], [], [], []
-    for s in range(S):
-        a = torch.from_numpy(acts[s]).cuda()
-        out = g.step(a)
-        assert g.step_kernel() == _abi.KERNEL_UNITS, "the units kernel must be the one under test"
-        w = torch.cat([out["obs_blue"].reshape(E, -1), out["obs_red"].reshape(E, -1)], 1)
-        w = w.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
-        hs.append((w * mt).sum(1).cpu().numpy().view(np.uint64))
-        rews.append(torch.cat([out["rew_blue"], out["rew_red"]], 1).cpu().numpy())
-        dones.append(out["done"].cpu().numpy().copy())
-        cogs.append(out["cog"].cpu().numpy().copy())
-        after.append(a.cpu().numpy())
-    torch.cuda.synchronize()
+    mult = hash_mult(2 * 4 * 68, seed=5)
+    gpu = _gpu_run(g, acts, mult, after=True, kernel=_abi.KERNEL_UNITS)
     assert int((g.env_state()["err"] != 0).sum()) == 0
     g.close()
     oh, orw, od, oc, oa = _oracle.fullsize(grid, 4, 4, [0] * 4 + [1] * 4, pos, acts, mult, seed, 40,
                                            pos_per_env=True, trained_red=trained_red,
                                            acts_after=True)
-    gh, gr, gd, gc, ga = map(np.stack, (hs, rews, dones, cogs, after))
-    bad = np.argwhere(gh != oh)
-    assert bad.size == 0, f"{len(bad)} (step, env) observation hashes differ, first {bad[:6].tolist()}"
-    assert np.array_equal(gd, od), np.argwhere(gd != od)[:6].tolist()
+    gd, ga = gpu[2], gpu[4]
+    _compare(gpu[:4], (oh, orw, od, oc), "units")
     assert np.array_equal(ga, oa), np.argwhere((ga != oa).any(-1))[:6].tolist()
-    assert np.allclose(gr, orw, rtol=0, atol=REW_TOL)
-    assert np.allclose(gc, oc, rtol=0, atol=1e-5, equal_nan=True)
     # what the layout is for: loud units fought (victories) and quiet ones ran
     # to the horizon, in both workgroups
     for w in range(2):

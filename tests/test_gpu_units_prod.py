@@ -29,13 +29,14 @@ import numpy as np
 import pytest
 import torch
 
+import _device as D
 import _move_rows as M
 import _oracle
 import _quiet_cases as Q
+from _spawns import REF_SPAWNS, grid as _grid
 
 pytestmark = pytest.mark.gpu
 
-REW_TOL = 1e-5  # the suite's reward tolerance (float32 outputs of float64 sums below 1 000)
 STEPS, HORIZON, SEED = 12, 5, 11
 E_SIM = 512
 TYPES = [_oracle.T_LARGE] * 8
@@ -52,9 +53,9 @@ ENV_KEYS = (("n_blue_left", "n_blue_left"), ("n_red_left", "n_red_left"), ("step
 def inputs(case, G=100):
     """pos [E_SIM, 8, 2], duct [E_SIM] (NaN: the reset's draw), acts [STEPS, E_SIM, 8, 4] float32,
     probes (envs meant to be loud)."""
-    grid = Q._grid(G)
+    grid = _grid(G)
     if case == "ref":
-        pos = np.array([Q.REF_SPAWNS] * E_SIM, np.int32)
+        pos = np.array([REF_SPAWNS] * E_SIM, np.int32)
         acts = np.random.default_rng(SEED).random((STEPS, E_SIM, 8, 4), dtype=np.float32)
         return pos, np.full(E_SIM, np.nan), acts, []
     if case == "mixed":
@@ -78,7 +79,7 @@ def oracle(case, mode="f32", G=100, E=E_SIM):
     """The oracle over envs 0..E-1 of a case's inputs (an env's record depends on
     its own index only, so a run of the first 256 envs reads the first 256).
     mode: f32 rows | f64 rows | i32 DISCRETE rows | tape (f32 rows, tape RNG)."""
-    grid = Q._grid(G)
+    grid = _grid(G)
     pos, duct, acts32, _ = inputs(case, G)
     discrete = mode == "i32"
     if discrete:  # DISCRETE rows: radar, salvo, cell index, unused (the parity test's ranges)
@@ -94,10 +95,8 @@ def oracle(case, mode="f32", G=100, E=E_SIM):
     kinds = np.full(8, kind, np.int32)
     tape, offs = _tape(E) if mode == "tape" else (None, None)
     S = STEPS
-    out = dict(obs_blue=np.zeros((S, E, 4, 68), np.float32), obs_red=np.zeros((S, E, 4, 68), np.float32),
-               rew_blue=np.zeros((S, E, 4)), rew_red=np.zeros((S, E, 4)), done=np.zeros((S, E), np.int32),
-               cog=np.zeros((S, E)), acts_after=np.zeros(acts.shape, acts.dtype)[:, :E],
-               ctr=np.zeros((S, E), np.int64), loud=np.zeros((S, E), bool), reset=np.zeros((S, E), bool),
+    out = _oracle.new_record(S, E, 4, 4, acts.dtype)
+    out.update(ctr=np.zeros((S, E), np.int64), loud=np.zeros((S, E), bool), reset=np.zeros((S, E), bool),
                err=np.zeros(E, np.int64), ducting=np.zeros(E), pos=np.zeros((E, 8, 2), np.int64))
     for k in ("radar", "missiles", "alive", "steps_done", "dist_lz", "tl_cnt"):
         out[k] = np.zeros((E, 8))
@@ -120,11 +119,7 @@ def oracle(case, mode="f32", G=100, E=E_SIM):
             ctr = "tape_pos" if tape is not None else "ctr"
             # loud by the oracle alone: the step drew (an EW bearing, a shot) or left a target list
             out["loud"][s, e] = st1[ctr] != st0[ctr] or bool(o.agents()["tl_cnt"].any())
-            for k in ("obs_blue", "obs_red"):
-                out[k][s, e] = r[k].astype(np.float32)
-            out["rew_blue"][s, e], out["rew_red"][s, e] = r["rew_blue"], r["rew_red"]
-            out["done"][s, e], out["cog"][s, e] = r["done"], r["cog"]
-            out["acts_after"][s, e] = r["actions_after"].astype(acts.dtype)
+            _oracle.record_step(out, s, e, r)
             t += 1
             if r["done"] == 0 or t >= HORIZON:  # the device's auto-reset
                 o.reset(TYPES, pos[e])
@@ -148,73 +143,36 @@ def oracle(case, mode="f32", G=100, E=E_SIM):
 # ---------------------------------------------------------------------------
 def _game(E, monkeypatch, *, G=100, env=None, discrete=False, reward_dtype=torch.float32):
     """A 4v4 handle with 5-step episodes; `env`: knobs read by lnw_create."""
-    from lnw.batched import BatchedGame
     from lnw.config import Scenario
-    for k, v in (env or {}).items():
-        monkeypatch.setenv(k, v)
     sc = Scenario(landing_ops=False, auto_reset=True, episode_steps=HORIZON, discrete=discrete)
-    g = BatchedGame(E, ["large"] * 4, ["large"] * 4, scenario=sc, grid=Q._grid(G), seed=SEED,
-                    reward_dtype=reward_dtype)
-    for k in env or {}:
-        monkeypatch.delenv(k, raising=False)
-    assert g.set_epw(64) == 64
-    return g
+    return D.make_game(monkeypatch, E, ["large"] * 4, ["large"] * 4, sc, _grid(G), SEED, env=env, epw=64,
+                       reward_dtype=reward_dtype)
 
 
 def _start(g, case, G=100, tape=False):
-    from lnw._abi import F_DUCT
-    E = g.E
     pos, duct, _, _ = inputs(case, G)
-    if tape:
-        g.set_tape(*_tape(E))
-    else:
-        g.set_rng(SEED)
-    g.reset(positions=Q.REF_SPAWNS, pos_per_env=torch.from_numpy(pos[:E].copy()))
-    d = g.get(F_DUCT).cpu().numpy()
-    fixed = ~np.isnan(duct[:E])
-    d[fixed] = duct[:E][fixed]
-    g.set(F_DUCT, torch.from_numpy(d))
-
-
-def _first(bad):
-    return np.argwhere(bad)[:4].tolist()
+    D.start(g, pos, seed=SEED, tape=_tape(g.E) if tape else None, duct=duct, positions=REF_SPAWNS)
 
 
 def _run(g, sim, tag, *, prod, kernels, row_kind=False):
     """Step the device over the case's actions; every env and step against the
     oracle's record `sim`, then the state left behind. Returns the outputs."""
-    from lnw._abi import F_RNG
     E = g.E
     kept = []
     rk = torch.full((E, 8), sim["kind"], dtype=torch.uint8).cuda() if row_kind else None
     for s in range(STEPS):
-        act = torch.from_numpy(sim["acts"][s, :E].copy()).cuda()
-        out = {k: v.cpu().numpy().copy() for k, v in g.step(act, rk).items()}
+        out = D.step(g, sim["acts"][s, :E], rk, extra=("ctr",))
         assert g.step_kernel() in kernels, (tag, g.step_kernel())
         assert g.step_kernel_prod() == prod, (tag, "production kernel", g.step_kernel_prod())
-        after = act.cpu().numpy()
-        out["acts_after"] = after
-        for k in ("obs_blue", "obs_red"):  # bit for bit
-            bad = (out[k].view(np.int32) != sim[k][s, :E].view(np.int32)).any(axis=(1, 2))
-            assert not bad.any(), (tag, s, k, "envs", _first(bad))
-        for k in ("rew_blue", "rew_red"):
-            bad = (np.abs(out[k] - sim[k][s, :E]) > REW_TOL).any(axis=1)
-            assert not bad.any(), (tag, s, k, "envs", _first(bad))
-        assert np.array_equal(out["done"], sim["done"][s, :E]), (tag, s, "done", _first(out["done"] != sim["done"][s, :E]))
-        cg, oc = out["cog"], sim["cog"][s, :E]
-        bad = ~((np.abs(cg - oc) <= 1e-5) | (np.isnan(cg) & np.isnan(oc)))
-        assert not bad.any(), (tag, s, "cog", _first(bad))
-        assert np.array_equal(after.view(np.uint8), sim["acts_after"][s, :E].view(np.uint8)), (tag, s, "action rows")
-        bad = g.get(F_RNG).cpu().numpy() != sim["ctr"][s, :E]
-        assert not bad.any(), (tag, s, "draw counter", _first(bad))
+        D.assert_step(out, sim, s, tag, rew="tol", cog="tol")
         kept.append(out)
     es, ag = g.env_state(), g.agents()
     assert np.array_equal(es["err"].astype(np.int64), sim["err"][:E]), (tag, "error flags")
     assert np.array_equal(es["ducting"], sim["ducting"][:E]), (tag, "ducting")
     for dk, ok in ENV_KEYS:
-        assert np.array_equal(es[dk], sim["env_" + ok][:E]), (tag, dk, _first(es[dk] != sim["env_" + ok][:E]))
+        assert np.array_equal(es[dk], sim["env_" + ok][:E]), (tag, dk, D.first(es[dk] != sim["env_" + ok][:E]))
     dpos = np.stack([ag["x"], ag["y"]], -1)
-    assert np.array_equal(dpos, sim["pos"][:E]), (tag, "cells", _first((dpos != sim["pos"][:E]).any(-1)))
+    assert np.array_equal(dpos, sim["pos"][:E]), (tag, "cells", D.first((dpos != sim["pos"][:E]).any(-1)))
     for k in ("radar", "missiles", "alive", "steps_done", "dist_lz", "tl_cnt"):
         assert np.array_equal(ag[k].astype(np.float64), sim[k][:E]), (tag, k)
     return kept

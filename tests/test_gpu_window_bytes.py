@@ -25,10 +25,11 @@ import functools
 
 import numpy as np
 import pytest
-import torch
 
+import _device as D
 import _oracle
 import _quiet_cases as Q
+from _spawns import box_positions, grid as _grid
 
 pytestmark = pytest.mark.gpu
 
@@ -91,28 +92,20 @@ def redeal(grid, shown):
     return out
 
 
-def _box_positions(grid, E, nb, nr, seed, box_b, box_r):
-    rng = np.random.default_rng(seed)
-    water = lambda x0, x1, y0, y1: [(x, y) for x in range(x0, x1) for y in range(y0, y1) if grid[x, y] <= 74]
-    wb, wr = water(*box_b), water(*box_r)
-    return np.array([[wb[i] for i in rng.integers(0, len(wb), nb)] +
-                     [wr[i] for i in rng.integers(0, len(wr), nr)] for _ in range(E)], np.int32)
-
-
 @functools.lru_cache(maxsize=None)
 def inputs(name):
     """grid (dealt again), pos [E, A, 2], acts [steps, E, A, 4] float32, per-env
     ducting (NaN: the reset's draw) and the seed. Cached and left unchanged."""
     cs = CASES[name]
     nb, nr = len(cs["blue"]), len(cs["red"])
-    base = Q._grid(cs["G"])
+    base = _grid(cs["G"])
     if cs["form"]:
         sim = Q.form_sim(cs["form"], Q.REACH_SEEDS[0])
         pos, duct, acts, seed = sim["pos"], sim["duct"], sim["acts"][:cs["steps"]], Q.REACH_SEEDS[0]
     else:
         seed = 11
         box_b, box_r = (BOX_B200, BOX_R200) if cs["G"] == 200 else (BOX_B, BOX_R)
-        pos = _box_positions(base, cs["E"], nb, nr, 5, box_b, box_r)
+        pos = box_positions(base, cs["E"], nb, nr, 5, box_b, box_r)
         duct = np.full(cs["E"], np.nan)
         acts = np.random.default_rng(100 + nb).random((cs["steps"], cs["E"], nb + nr, 4), dtype=np.float32)
     # the cells that show in a window, from a run on the fixture's own values
@@ -225,39 +218,18 @@ def test_every_window_class_is_covered():
 
 @pytest.mark.parametrize("name", list(CASES))
 def test_rows_equal_oracle(name, monkeypatch):
-    from lnw import _abi
-    from lnw.batched import BatchedGame
-    from lnw._abi import F_DUCT
     from lnw.config import Scenario
     cs, inp = CASES[name], inputs(name)
-    want = oracle_rows(name)
+    want = dict(zip(("obs_blue", "obs_red"), oracle_rows(name)))
     _check_conditions(name)  # from the oracle's rows alone, before any device call
-    E = inp["E"]
     f = Q.FORMS[cs["form"]] if cs["form"] else None
     env = list(cs["env"]) + ([f["env"]] if f and f["env"] else [])
-    for k in env:
-        monkeypatch.setenv(k, "1")
     sc = Scenario(landing_ops=cs["landing_ops"], los_mode=cs["los_mode"])
-    g = BatchedGame(E, cs["blue"], cs["red"], scenario=sc, grid=inp["grid"], seed=inp["seed"])
-    for k in env:
-        monkeypatch.delenv(k, raising=False)
-    epw = f["epw"] if f else cs["epw"]
-    if epw:
-        assert g.set_epw(epw) == epw
-    if cs["contact"]:
-        g.set_variant(True)
-    g.set_rng(inp["seed"])
-    g.reset(positions=inp["pos"][0], pos_per_env=torch.from_numpy(inp["pos"]))
-    if not np.isnan(inp["duct"]).all():
-        duct = g.get(F_DUCT).cpu().numpy()
-        m = ~np.isnan(inp["duct"])
-        duct[m] = inp["duct"][m]
-        g.set(F_DUCT, torch.from_numpy(duct))
+    g = D.make_game(monkeypatch, inp["E"], cs["blue"], cs["red"], sc, inp["grid"], inp["seed"],
+                    env=dict.fromkeys(env, "1"), epw=f["epw"] if f else cs["epw"], contact=cs["contact"])
+    D.start(g, inp["pos"], seed=inp["seed"], duct=inp["duct"])
     for s in range(cs["steps"]):
-        out = g.step(torch.from_numpy(inp["acts"][s]).cuda())
-        for k, w in zip(("obs_blue", "obs_red"), want):
-            got = out[k].cpu().numpy()
-            assert np.array_equal(got, w[s]), (name, s, k, np.argwhere((got != w[s]).any(axis=(1, 2)))[:4].tolist())
-    assert g.step_kernel() == getattr(_abi, "KERNEL_" + cs["kernel"])
+        D.assert_step(D.step(g, inp["acts"][s]), want, s, name)  # the rows alone, bit for bit
+    assert g.step_kernel() == D.kernel_code(cs["kernel"])
     assert not g.env_state()["err"].any()
     g.close()

@@ -8,24 +8,12 @@ ValueError / OverflowError of round() on a NaN / inf fix (:146), move target
 (:470), engagement threshold (:528) or radar action (:558) -> LNW_ERRF_NAN_ROUND.
 The GPU path is compared with the oracle on the same episodes, crash steps and
 the steps after them included, in tests/test_gpu_crash_modes.py."""
-import json
-
 import numpy as np
 import pytest
 
 import _oracle
-
-ERRF_ZERODIV, ERRF_NAN_ROUND = 1, 2
-EXC_BIT = {"ZeroDivisionError": ERRF_ZERODIV, "ValueError": ERRF_NAN_ROUND,
-           "OverflowError": ERRF_NAN_ROUND}
-
-
-def crash_cases():
-    fx = np.load(_oracle.GOLDEN + "/crash_modes.npz")
-    return fx, {m["name"]: m for m in json.loads(str(fx["meta"]))}
-
-
-FX, META = crash_cases()
+from _crash_cases import EXC_BIT, FX, META
+from _spawns import grid as _grid
 
 
 def oracle_run(grid, m, fx):
@@ -45,7 +33,7 @@ def oracle_run(grid, m, fx):
 
 @pytest.mark.parametrize("name", sorted(META))
 def test_oracle_flags_reference_crash(name):
-    grid = np.load(_oracle.GOLDEN + "/grids.npz")["grid100"]
+    grid = _grid(100)
     m = META[name]
     res = oracle_run(grid, m, FX)
     crash = m["crash"]

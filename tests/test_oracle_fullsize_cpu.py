@@ -5,6 +5,7 @@ sum_k bits(float32 obs[k]) * mult[k] mod 2^64 recomputed in numpy. CPU only."""
 import numpy as np
 
 import _oracle
+from _spawns import grid as _grid
 
 
 def _hash(ob, orr, mult):
@@ -14,7 +15,7 @@ def _hash(ob, orr, mult):
 
 
 def test_fullsize_driver_matches_per_env_oracle():
-    g = _oracle.load_fixture("grids.npz")["grid100"]
+    g = _grid(100)
     E, S, seed, horizon = 12, 23, 5, 10
     rng = np.random.default_rng(0)
     water = np.argwhere(g[30:70, 40:65] <= 74) + np.array([30, 40])

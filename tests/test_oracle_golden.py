@@ -14,14 +14,14 @@ import pytest
 from _oracle import (GOLDEN, K_F32, K_F64, OracleEnv, astar_batch, episode_meta,
                      fixture_kinds, load_fixture, los_batch, move_batch)
 import _oracle
+from _spawns import grids as _grids
 
 EPISODES = sorted(os.path.basename(p) for p in glob.glob(os.path.join(GOLDEN, "ep_*.npz")))
 
 
 @pytest.fixture(scope="module")
 def grids():
-    g = load_fixture("grids.npz")
-    return [g["grid100"], g["grid200"]]
+    return list(_grids())
 
 
 def test_grid_fixture(grids):

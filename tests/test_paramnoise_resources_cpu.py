@@ -6,11 +6,7 @@ recomputed from blockIdx at each use and their row indices are 32-bit, so
 nothing more lives across the conv head than in the plain kernels), and
 lnw_actor_perturb's kernel holds no scratch at all (it picks one of a Philox
 block's four values with selects, not by indexing a register array)."""
-import os
-
-import pytest
-
-from test_kernel_resources_cpu import LIB, _tool, kernel_scratch
+from _codeobj import LIB, kernel_scratch, needs_lib, needs_tools
 
 # mangled-name fragment -> largest scratch allowed (bytes per lane)
 LIMITS = {
@@ -22,11 +18,10 @@ LIMITS = {
 }
 
 
-@pytest.mark.skipif(not os.path.exists(LIB), reason="liblnw.so not built")
-@pytest.mark.skipif(not (_tool("llvm-objcopy") and _tool("clang-offload-bundler") and _tool("llvm-readelf")),
-                    reason="ROCm LLVM tools not found")
-def test_paramnoise_kernels_scratch(tmp_path):
-    sc = kernel_scratch(LIB, str(tmp_path))
+@needs_lib
+@needs_tools
+def test_paramnoise_kernels_scratch():
+    sc = kernel_scratch(LIB)
     for frag, limit in LIMITS.items():
         hits = {k: v for k, v in sc.items() if frag in k}
         assert len(hits) == 1, f"kernel {frag}: {sorted(hits)}"

@@ -2,11 +2,7 @@
 the in-tree liblnw.so exactly as test_ppolearn_resources_cpu.py does: none of
 them spills (the key is a Philox block, a polynomial and a double division per
 lane; the select, the compaction and the sort hold a handful of values)."""
-import os
-
-import pytest
-
-from test_kernel_resources_cpu import LIB, _tool, kernel_scratch
+from _codeobj import LIB, kernel_scratch, needs_lib, needs_tools
 
 LIMITS = {
     "ps_init_kernel": 0,
@@ -20,11 +16,10 @@ LIMITS = {
 }
 
 
-@pytest.mark.skipif(not os.path.exists(LIB), reason="liblnw.so not built")
-@pytest.mark.skipif(not (_tool("llvm-objcopy") and _tool("clang-offload-bundler") and _tool("llvm-readelf")),
-                    reason="ROCm LLVM tools not found")
-def test_ppo_sample_kernels_scratch(tmp_path):
-    sc = kernel_scratch(LIB, str(tmp_path))
+@needs_lib
+@needs_tools
+def test_ppo_sample_kernels_scratch():
+    sc = kernel_scratch(LIB)
     for frag, limit in LIMITS.items():
         hits = {k: v for k, v in sc.items() if frag in k}
         assert hits, f"kernel {frag} not in liblnw.so"

@@ -3,11 +3,7 @@ in-tree liblnw.so exactly as test_qlearn_resources_cpu.py does: none of them
 spills. The per-row conv passes hold a 49-value conv1 map or four 9-value conv2
 maps in registers at 128 threads per workgroup (DESIGN.md "MAPPO learner"); a
 spill there would sit inside the rolled channel loops."""
-import os
-
-import pytest
-
-from test_kernel_resources_cpu import LIB, _tool, kernel_scratch
+from _codeobj import LIB, kernel_scratch, needs_lib, needs_tools
 
 LIMITS = {
     "pl_features_kernel": 0,
@@ -30,11 +26,10 @@ LIMITS = {
 }
 
 
-@pytest.mark.skipif(not os.path.exists(LIB), reason="liblnw.so not built")
-@pytest.mark.skipif(not (_tool("llvm-objcopy") and _tool("clang-offload-bundler") and _tool("llvm-readelf")),
-                    reason="ROCm LLVM tools not found")
-def test_ppolearn_kernels_scratch(tmp_path):
-    sc = kernel_scratch(LIB, str(tmp_path))
+@needs_lib
+@needs_tools
+def test_ppolearn_kernels_scratch():
+    sc = kernel_scratch(LIB)
     for frag, limit in LIMITS.items():
         hits = {k: v for k, v in sc.items() if frag in k}
         assert hits, f"kernel {frag} not in liblnw.so"

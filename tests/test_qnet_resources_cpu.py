@@ -3,11 +3,7 @@ test_kernel_resources_cpu.py: qnet_act_kernel (both instantiations) spills one
 32-bit value around the conv head, 8 B per lane at 256 VGPRs and two waves per
 SIMD, below the 20 B the policy kernel is allowed; untrained red's kernel has
 none."""
-import os
-
-import pytest
-
-from test_kernel_resources_cpu import LIB, _tool, kernel_scratch
+from _codeobj import LIB, kernel_scratch, needs_lib, needs_tools
 
 LIMITS = {
     "qnet_act_kernelILi32E": 8,
@@ -16,11 +12,10 @@ LIMITS = {
 }
 
 
-@pytest.mark.skipif(not os.path.exists(LIB), reason="liblnw.so not built")
-@pytest.mark.skipif(not (_tool("llvm-objcopy") and _tool("clang-offload-bundler") and _tool("llvm-readelf")),
-                    reason="ROCm LLVM tools not found")
-def test_qnet_kernels_scratch(tmp_path):
-    sc = kernel_scratch(LIB, str(tmp_path))
+@needs_lib
+@needs_tools
+def test_qnet_kernels_scratch():
+    sc = kernel_scratch(LIB)
     for frag, limit in LIMITS.items():
         hits = {k: v for k, v in sc.items() if frag in k}
         assert hits, f"kernel {frag} not in liblnw.so"

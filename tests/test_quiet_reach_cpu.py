@@ -56,7 +56,7 @@ def test_layout_shape():
                 lanes |= {e % epw for e in probes[:2]}
             far = np.setdiff1d(np.arange(E), probes)
             assert np.isnan(duct[far]).all() and set(duct[probes]) <= set(Q.DUCTS)
-            assert (pos[far] == np.array(Q.REF_SPAWNS[:nb] + Q.REF_SPAWNS[4:4 + nb])).all()
+            assert (pos[far] == np.array(Q.ref_spawns(nb))).all()
             for e in probes:
                 assert all(grid[x, y] <= 74 for x, y in pos[e]), (name, seed, e)
         if not f["units"]:

@@ -13,16 +13,11 @@ segment is 992 B, and every instantiation spills less than it did. The bounds
 below are the parent's figures (never to be reached again) and what this
 layout reached (so that growth shows up here).
 """
-import os
-import re
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "littoral-naval-warfare-marl_amd", "lnw", "liblnw.so")
-LLVM = "/opt/rocm/lib/llvm/bin"
+from _codeobj import LIB, kernel_metadata, needs_lib, needs_tools
+
+pytestmark = [needs_lib, needs_tools]
 
 PARENT_KERNARG = 1128
 REACHED_KERNARG = 992
@@ -46,53 +41,9 @@ STEP_KERNELS = {
 SCRATCH_LIMIT = {"ILi4ELi4ELb0ELb0ELi4ELb0ELb0EE": 0, "ILi4ELi4ELb0ELb0ELi1ELb0ELb0EE": 28}
 
 
-def _tool(name):
-    p = os.path.join(LLVM, name)
-    return p if os.path.exists(p) else shutil.which(name)
-
-
-def kernel_metadata(lib, tmp, keys):
-    """{kernel name: {key: int}} over every code object in the library's
-    .hip_fatbin (one offload bundle per translation unit)."""
-    fat = os.path.join(tmp, "fat.bin")
-    subprocess.run([_tool("llvm-objcopy"), f"--dump-section=.hip_fatbin={fat}", lib,
-                    os.path.join(tmp, "host.so")], check=True, capture_output=True)
-    data = open(fat, "rb").read()
-    magic = b"__CLANG_OFFLOAD_BUNDLE__"
-    starts = [m.start() for m in re.finditer(re.escape(magic), data)]
-    out = {}
-    for n, a in enumerate(starts):
-        b = starts[n + 1] if n + 1 < len(starts) else len(data)
-        part, co = os.path.join(tmp, f"b{n}.bin"), os.path.join(tmp, f"co{n}.o")
-        with open(part, "wb") as f:
-            f.write(data[a:b])
-        subprocess.run([_tool("clang-offload-bundler"), "--unbundle", "--type=o", f"--input={part}",
-                        "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"],
-                       check=True, capture_output=True)
-        notes = subprocess.run([_tool("llvm-readelf"), "--notes", co], check=True, capture_output=True,
-                               text=True).stdout
-        # one "- .agpr_count: ..." list item per kernel under amdhsa.kernels
-        for item in re.split(r"\n\s*- \.agpr_count:", notes)[1:]:
-            m = re.search(r"\.name:\s+(\S+)", item)
-            if not m:
-                continue
-            vals = {}
-            for k in keys:
-                v = re.search(r"\.%s:\s+(\d+)" % re.escape(k), item)
-                if v:
-                    vals[k] = int(v.group(1))
-            out[m.group(1)] = vals
-    return out
-
-
 @pytest.fixture(scope="module")
-def step_meta(tmp_path_factory):
-    if not os.path.exists(LIB):
-        pytest.skip("liblnw.so not built")
-    if not (_tool("llvm-objcopy") and _tool("clang-offload-bundler") and _tool("llvm-readelf")):
-        pytest.skip("ROCm LLVM tools not found")
-    md = kernel_metadata(LIB, str(tmp_path_factory.mktemp("co")),
-                         ("kernarg_segment_size", "sgpr_spill_count", "private_segment_fixed_size"))
+def step_meta():
+    md = kernel_metadata(LIB, ("kernarg_segment_size", "sgpr_spill_count", "private_segment_fixed_size"))
     return {k: v for k, v in md.items() if "step_kernelI" in k}
 
 

@@ -12,7 +12,9 @@ kernel stays in the library: every other configuration runs it.
 """
 import pytest
 
-from test_step_args_cpu import LIB, _tool, kernel_metadata
+from _codeobj import LIB, kernel_metadata, needs_lib, needs_tools
+
+pytestmark = [needs_lib, needs_tools]
 
 GENERIC = "step_kernelILi4ELi4ELb0ELb0ELi4ELb0ELb0EE"  # step_kernel<4, 4, false, false, 4>
 PROD = "step_units_prod_kernel"
@@ -21,13 +23,8 @@ KEYS = ("sgpr_spill_count", "vgpr_spill_count", "private_segment_fixed_size", "v
 
 
 @pytest.fixture(scope="module")
-def meta(tmp_path_factory):
-    import os
-    if not os.path.exists(LIB):
-        pytest.skip("liblnw.so not built")
-    if not (_tool("llvm-objcopy") and _tool("clang-offload-bundler") and _tool("llvm-readelf")):
-        pytest.skip("ROCm LLVM tools not found")
-    md = kernel_metadata(LIB, str(tmp_path_factory.mktemp("co")), KEYS)
+def meta():
+    md = kernel_metadata(LIB, KEYS)
     gen = [v for k, v in md.items() if GENERIC in k]
     prod = [v for k, v in md.items() if PROD in k]
     assert len(gen) == 1, "the generic units kernel must stay in liblnw.so"
@@ -35,10 +32,10 @@ def meta(tmp_path_factory):
     return gen[0], prod[0]
 
 
-def test_name_is_not_a_step_kernel_instantiation(meta, tmp_path):
+def test_name_is_not_a_step_kernel_instantiation(meta):
     """test_step_args_cpu.py lists every step_kernel<...> instantiation; the new
     kernel has a name of its own and is no entry of that list."""
-    md = kernel_metadata(LIB, str(tmp_path), ("sgpr_spill_count",))
+    md = kernel_metadata(LIB, ("sgpr_spill_count",))
     names = [k for k in md if PROD in k]
     assert names and all("step_kernelI" not in k for k in names)
 
