@@ -441,7 +441,7 @@ int lnw_create(const lnw_params *params, int32_t n_envs, int32_t nb, int32_t nr,
   // the shipped library honours only the knobs that change the launch shape or
   // code path, never the results (bit 9: no quiet path, 15: the group kernel's
   // fire loop entry by entry, 17: per-lane bearing loop, 22/23: where the
-  // head's loads are issued, 28: the per-env quiet test in small workgroups,
+  // head's loads are issued (22: the staged quiet forms' first pass only), 28: the per-env quiet test in small workgroups,
   // 29: their env counters loaded in phase Q); section skips and
   // replaced arithmetic exist only in the diagnostics build (-DLNW_DIAG,
   // lnw.build.build_diag)

@@ -546,7 +546,7 @@ __device__ __forceinline__ void quiet_step_t(const KParams &P, const KState &S, 
   // wave 1 takes pass 0 (envs 0..7, blue rows) and loads its window records now,
   // from the final cells phase M left (pos_new when it moved, else pos_old: the
   // cells quiet_moves_t commits), so they are in flight across phase Q
-  // (LNW_DEBUG_SKIP bit 22: claimed and loaded after the barrier instead)
+  // (LNW_DEBUG_SKIP bit 22: in the staged forms, claimed and loaded after the barrier instead)
   const bool early = !(P.dbg_skip & 4194304);
   // small workgroups (nenv * NB <= 64 lanes: config 2 and config 3's per-GPU
   // shard run 16 envs per workgroup): wave 1 builds every row itself, lane
@@ -558,7 +558,10 @@ __device__ __forceinline__ void quiet_step_t(const KParams &P, const KState &S, 
   // (two slabs of 64 / NB envs when the host gave the launch qbig stages for
   // wider workgroups: step_qdirect, P.qdirect; the pair-lane tail needs the
   // narrow form, spread)
-  const bool direct = (SL ? P.qdirect != 0 : P.epw * NB <= WAVE) && P.los_mode == 0 && early;
+  // (not a matter of `early`: bit 22 moves the staged forms' first pass only. A
+  // direct form that it turned into a staged one kept spread, skipped the moved /
+  // kinds fill below and paid every moved ship reward 0 instead of 1)
+  const bool direct = (SL ? P.qdirect != 0 : P.epw * NB <= WAVE) && P.los_mode == 0;
   const bool spread = P.epw * NB <= WAVE;
   f32x4 v[12], vr[12];
   float w48 = 0.0f, wr48 = 0.0f;

@@ -63,6 +63,17 @@ enum {
     ORC_ST_LS_REWARD,     /* reward evaluations of a live landing ship */
     ORC_ST_ERR,           /* OR of the env's error flags */
     ORC_ST_RESETS,        /* auto-resets (orc_fullsize_range) */
+    ORC_ST_BEARINGS,      /* EW bearings taken */
+    ORC_ST_DEF_IN,        /* defensive reward after step 14: inside the zone (+1) */
+    ORC_ST_DEF_OUT,       /* ... outside it (-2) */
+    ORC_ST_LANDINGS,      /* steps ended by a landing ship on its zone */
+    ORC_ST_LS_DIST0,      /* landing-ship reward evaluations at distance 0 */
+    ORC_ST_LS_SUNK_END,   /* steps ended by all landing ships sunk */
+    ORC_ST_NEUT_PEN,      /* neutralised penalties applied to a side (- 5 * losses) */
+    ORC_ST_AGG_FIRED,     /* scripted red's aggression draws below RED_AGGRESSION */
+    ORC_ST_AGG_HELD,      /* ... and not below it */
+    ORC_ST_BLUE_VICT,     /* increments of blue_victory over all episodes */
+    ORC_ST_RED_VICT,      /* increments of red_victory over all episodes */
     ORC_NSTATS
 };
 
@@ -607,6 +618,7 @@ static void get_obs(orc_env *e, int a, double *out) {
                 if (!seen) {
                     /* calculate_bearing (combatant.py:249-263) */
                     double bearing = py_degrees(atan2((double)ddy, (double)ddx));
+                    e->stat[ORC_ST_BEARINGS]++;
                     if (ddy < 0) e->stat[ORC_ST_BEAR_DYNEG]++;
                     if (abs(ddx) > 40 || abs(ddy) > 40) e->stat[ORC_ST_BEAR_FAR]++;
                     double distortion = rng_gauss(e);
@@ -866,8 +878,13 @@ static double calculate_reward(orc_env *e, int a, int movement, int engage, int 
     reward += (double)(n_hit * 10);
     if (u->side == 1 && u->type != T_LS && !e->P.aggressive) {
         if (u->steps_done > 14) {
-            if (u->x < 19 || u->x > 55 || u->y < 40 || u->y > 70) reward = fmax(reward - 2.0, 0.0);
-            else reward += 1.0;
+            if (u->x < 19 || u->x > 55 || u->y < 40 || u->y > 70) {
+                reward = fmax(reward - 2.0, 0.0);
+                e->stat[ORC_ST_DEF_OUT]++;
+            } else {
+                reward += 1.0;
+                e->stat[ORC_ST_DEF_IN]++;
+            }
         }
     }
     if (u->side == 1 && e->P.aggressive && u->type != T_LS) {
@@ -888,7 +905,7 @@ static double calculate_reward(orc_env *e, int a, int movement, int engage, int 
         } else {
             reward += 100.0;
         }
-        if (dl == 0) reward += 100.0;
+        if (dl == 0) { reward += 100.0; e->stat[ORC_ST_LS_DIST0]++; }
         else reward += log10(100.0 / dl) * 5.0;
     }
     return reward;
@@ -933,7 +950,9 @@ int orc_step(orc_env *e, double *act, const int *kinds, double *obs_b, double *o
         int k = kinds ? kinds[g] : K_F64;
         int mv, eg, nd;
         if (!e->P.trained_red) {
-            if (rng_uniform(e) < e->P.red_aggression) {
+            int fired = rng_uniform(e) < e->P.red_aggression;
+            e->stat[fired ? ORC_ST_AGG_FIRED : ORC_ST_AGG_HELD]++;
+            if (fired) {
                 double v = rng_uniform(e);
                 if (k == K_F32) v = (double)(float)v;
                 else if (k == K_PYINT) v = trunc(v);
@@ -952,6 +971,7 @@ int orc_step(orc_env *e, double *act, const int *kinds, double *obs_b, double *o
             rew_r[a] = r;
         }
     }
+    const int bv0 = e->blue_victory, rv0 = e->red_victory;
     int blue_new_losses = e->neut_n[0];
     e->n_blue_left -= blue_new_losses;
     int red_new_losses = e->neut_n[1];
@@ -962,10 +982,14 @@ int orc_step(orc_env *e, double *act, const int *kinds, double *obs_b, double *o
     for (int a = 0; a < nr; a++)
         if (!eng_r[a] && alive0[nb + a]) rew_r[a] += (double)(red_hits * 2);
     if (!e->P.aggressive) {
-        if (blue_new_losses > 0)
+        if (blue_new_losses > 0) {
+            e->stat[ORC_ST_NEUT_PEN]++;
             for (int a = 0; a < nb; a++) rew_b[a] = fmax(rew_b[a] - (double)(blue_new_losses * 5), 0.0);
-        if (red_new_losses > 0)
+        }
+        if (red_new_losses > 0) {
+            e->stat[ORC_ST_NEUT_PEN]++;
             for (int a = 0; a < nr; a++) rew_r[a] = fmax(rew_r[a] - (double)(red_new_losses * 5), 0.0);
+        }
     }
     if (no_blue && !no_red) {
         done = 0;
@@ -985,10 +1009,11 @@ int orc_step(orc_env *e, double *act, const int *kinds, double *obs_b, double *o
         for (int a = 0; a < nr; a++) rew_r[a] += 10.0;
     }
     if (e->P.landing_ops) {
-        int rem = 0;
+        int rem = 0, landed = 0;
         for (int a = 0; a < nr; a++)
             if (e->s[nb + a].alive && e->s[nb + a].type == T_LS) rem++;
         if (!rem) {
+            e->stat[ORC_ST_LS_SUNK_END]++;
             done = 0;
             for (int a = 0; a < nb; a++) rew_b[a] += 100.0;
             for (int a = 0; a < nr; a++) rew_r[a] = rew_r[a] - rew_r[a];
@@ -998,13 +1023,17 @@ int orc_step(orc_env *e, double *act, const int *kinds, double *obs_b, double *o
                 orc_ship *s = &e->s[nb + a];
                 if (s->alive && s->type == T_LS && s->lz_x == s->x && s->lz_y == s->y) {
                     done = 0;
+                    landed = 1;
                     for (int q = 0; q < nb; q++) rew_b[q] = rew_b[q] - rew_b[q];
                     for (int q = 0; q < nr; q++) rew_r[q] += 100.0;
                     e->blue_victory++;
                 }
             }
         }
+        e->stat[ORC_ST_LANDINGS] += landed;
     }
+    e->stat[ORC_ST_BLUE_VICT] += e->blue_victory - bv0;
+    e->stat[ORC_ST_RED_VICT] += e->red_victory - rv0;
     e->steps_done++;
     for (int q = 0; q < e->neut_n[0]; q++) e->s[e->neut[0][q]].alive = 0;
     for (int q = 0; q < e->neut_n[1]; q++) e->s[nb + e->neut[1][q]].alive = 0;
@@ -1181,7 +1210,8 @@ int64_t orc_bench_range(const orc_params *P, const uint8_t *grid, int G, int nb,
 /* ------------------------------------------------------------------------ */
 /* Full-size parity driver (tests/test_gpu_fullsize.py only): the global    */
 /* envs [env0, env0 + n) of an E-env batch, Philox-seeded by global env id, */
-/* stepped S times with float32 actions acts[S][E][A][4] (row kind K_F32),  */
+/* stepped S times with float32 actions acts[S][E][A][4] (row_kind: K_F32,  */
+/* or K_PYINT for a discrete run, whose integer values float32 holds),      */
 /* auto-reset after done == 0 or `horizon` steps as the device does         */
 /* (lnw_kernels.hip phase W). Per (step, env) it records a 64-bit hash of   */
 /* the float32 observations, sum_k bits(obs[k]) * mult[k] mod 2^64 over the */
@@ -1194,8 +1224,9 @@ int64_t orc_bench_range(const orc_params *P, const uint8_t *grid, int G, int nb,
 void orc_fullsize_range(const orc_params *P, const uint8_t *grid, int G, int nb, int nr,
                         const int *types, const int *pos, int pos_per_env, const int *rand_ls,
                         uint64_t seed, int64_t E, int64_t env0, int64_t n, int S, int horizon,
-                        const float *acts, const uint64_t *mult, uint64_t *hash, float *rew,
-                        int32_t *done_out, float *cog_out, float *acts_after, int64_t *stats) {
+                        int row_kind, const float *acts, const uint64_t *mult, uint64_t *hash,
+                        float *rew, int32_t *done_out, float *cog_out, float *acts_after,
+                        int64_t *stats) {
     int A = nb + nr, Db = 4 * nb + 52, Dr = 4 * nr + 52;
     orc_env *e = (orc_env *)malloc(sizeof(orc_env));
     double *act = (double *)malloc(sizeof(double) * 4 * A);
@@ -1203,7 +1234,7 @@ void orc_fullsize_range(const orc_params *P, const uint8_t *grid, int G, int nb,
     double *ob = (double *)malloc(sizeof(double) * nb * Db);
     double *orr = (double *)malloc(sizeof(double) * nr * Dr);
     double rb[ORC_MAX_AGENTS], rr[ORC_MAX_AGENTS], cog;
-    for (int a = 0; a < A; a++) kinds[a] = K_F32;
+    for (int a = 0; a < A; a++) kinds[a] = row_kind;
     for (int64_t env = env0; env < env0 + n; env++) {
         const int *p = pos_per_env ? pos + env * A * 2 : pos;
         orc_env_init(e, P, grid, G, nb, nr);

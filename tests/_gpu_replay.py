@@ -17,7 +17,9 @@ def scenario_from_meta(meta, **over):
     F = meta["flags"]
     return Scenario(discrete=F["DISCRETE"], landing_ops=F["LANDING_OPS"], tactics=F["TACTICS"],
                     side=F["SIDE"], trained_red=F["TRAINED_RED"],
-                    red_aggression=F["RED_AGGRESSION"], **over)
+                    red_aggression=F["RED_AGGRESSION"],
+                    movement_threshold=F.get("MOVEMENT_THRESHOLD", 74), ew_threshold=F.get("EW_THRESHOLD", 70),
+                    landing_zone=tuple(meta.get("landing_zone", (14, 82))), **over)
 
 
 def replay_gpu(fx, grids, los_mode=0, move_mode=0, contact=False):

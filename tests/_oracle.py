@@ -71,7 +71,7 @@ def lib():
         L.orc_philox.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, P]
         L.orc_fullsize_range.argtypes = [P, P, C.c_int, C.c_int, C.c_int, P, P, C.c_int, P,
                                          C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_int,
-                                         C.c_int, P, P, P, P, P, P, P, P]
+                                         C.c_int, C.c_int, P, P, P, P, P, P, P, P]
         L.orc_np_mean.restype = C.c_double
         L.orc_np_mean.argtypes = [P, C.c_int]
         L.orc_get_stats.argtypes = [P, P]
@@ -135,7 +135,8 @@ def move_table(grid, type_code, R, starts, thr=74):
 
 # orc_fullsize_range's / orc_get_stats' per-env step statistics (ORC_ST_*)
 STATS = ("fix_lt8", "fix_eq8", "fix_gt8", "tl_max", "tl_past16", "bear_dyneg", "bear_far",
-         "ls_reward", "err", "resets")
+         "ls_reward", "err", "resets", "bearings", "def_in", "def_out", "landings", "ls_dist0",
+         "ls_sunk_end", "neut_pen", "agg_fired", "agg_held", "blue_vict", "red_vict")
 
 
 def np_mean(v):
@@ -280,13 +281,16 @@ def record_step(rec, s, e, r):
 # ---------------------------------------------------------------------------
 def fullsize(grid, nb, nr, types, pos, acts, mult, seed, horizon, *, pos_per_env=False,
              rand_ls=None, landing_ops=False, trained_red=True, acts_after=False, stats=False,
-             threads=None):
+             threads=None, discrete=False, aggressive=True, side_blue=True, red_aggression=0.4,
+             move_thr=74, ew_thr=70, lz=(14, 82)):
     """orc_fullsize_range over all E envs of acts [S, E, A, 4] (float32) on a
     thread pool (ctypes releases the GIL; ranges are disjoint): per (step, env)
     the observation hash (sum bits * mult mod 2^64), float32 rewards [S, E, A],
     done [S, E] and cog [S, E]; with acts_after=True also the action rows as
     each step left them [S, E, A, 4] (an untrained red's salvo write-back); with
-    stats=True, last, each env's step statistics [E, len(STATS)] (int64)."""
+    stats=True, last, each env's step statistics [E, len(STATS)] (int64).
+    discrete .. lz: the scenario's other options (orc_params); a discrete run's
+    rows are integer values held in float32, stepped as K_PYINT rows."""
     from concurrent.futures import ThreadPoolExecutor
     L = lib()
     S, E, A = acts.shape[:3]
@@ -296,7 +300,9 @@ def fullsize(grid, nb, nr, types, pos, acts, mult, seed, horizon, *, pos_per_env
     pos = np.ascontiguousarray(pos, np.int32)
     mult = np.ascontiguousarray(mult, np.uint64)
     rls = np.ascontiguousarray(rand_ls if rand_ls is not None else np.zeros(A), np.int32)
-    P = OrcParams(0, int(landing_ops), 1, 1, int(trained_red), 0.4, 74, 70, 14, 82)
+    P = OrcParams(int(discrete), int(landing_ops), int(aggressive), int(side_blue), int(trained_red),
+                  float(red_aggression), move_thr, ew_thr, lz[0], lz[1])
+    kind = K_PYINT if discrete else K_F32
     hsh = np.zeros((S, E), np.uint64)
     rew = np.zeros((S, E, A), np.float32)
     done = np.zeros((S, E), np.int32)
@@ -312,7 +318,7 @@ def fullsize(grid, nb, nr, types, pos, acts, mult, seed, horizon, *, pos_per_env
         if n:
             L.orc_fullsize_range(C.byref(P), _p(grid), grid.shape[0], nb, nr, _p(types), _p(pos),
                                  int(pos_per_env), _p(rls), seed, E, e0, n, S, horizon,
-                                 _p(acts), _p(mult), _p(hsh), _p(rew), _p(done), _p(cog),
+                                 kind, _p(acts), _p(mult), _p(hsh), _p(rew), _p(done), _p(cog),
                                  _p(aft) if aft is not None else None,
                                  _p(st) if st is not None else None)
     with ThreadPoolExecutor(threads) as ex:
@@ -322,7 +328,8 @@ def fullsize(grid, nb, nr, types, pos, acts, mult, seed, horizon, *, pos_per_env
 
 
 def rollout_env(grid, nb, nr, types, pos, acts, kinds, mult, seed, horizon, *, pos_per_env=False,
-                trained_red=False, threads=None):
+                trained_red=False, threads=None, discrete=False, aggressive=True, side_blue=True,
+                red_aggression=0.4, move_thr=74, ew_thr=70, lz=(14, 82)):
     """orc_rollout_range over all E envs: the env side of a MAPPO rollout
     (ppo.py:497-577) on the action arrays a device rollout stepped, acts
     [S, E, A, 4] float64 with row kinds [S, E, A]. Per (step, env): the hash of
@@ -338,7 +345,8 @@ def rollout_env(grid, nb, nr, types, pos, acts, kinds, mult, seed, horizon, *, p
     types = np.ascontiguousarray(types, np.int32)
     pos = np.ascontiguousarray(pos, np.int32)
     mult = np.ascontiguousarray(mult, np.uint64)
-    P = OrcParams(0, 0, 1, 1, int(trained_red), 0.4, 74, 70, 14, 82)
+    P = OrcParams(int(discrete), 0, int(aggressive), int(side_blue), int(trained_red),
+                  float(red_aggression), move_thr, ew_thr, lz[0], lz[1])
     hsh = np.zeros((S, E), np.uint64)
     rew = np.zeros((S, E, nb), np.float64)
     done = np.zeros((S, E), np.int32)

@@ -25,7 +25,8 @@ ep_<name>.npz   full episodes through ``Game.reset`` / ``Game.step``
                 locals with sys.settrace — no reference code is copied), and
                 the per-agent state after every step.
 
-Usage:  python tests/golden/make_golden.py [--quick] [episodes|los|...]
+Usage:  python tests/golden/make_golden.py [--quick] [episodes|options|los|...]
+        (options: only the scenario-option episodes of make_option_episodes)
         (LNW_GOLDEN_ONLY=ep1,ep2 limits the episode fixtures written)
 """
 import contextlib
@@ -362,16 +363,211 @@ def _snapshot(env, ships_all, nb):
     return pos, radar, miss, alive, steps, dlz, tl
 
 
+def _count_threshold_verdicts(combatant, landingship, counts):
+    """Wraps both ship classes' continuous_to_discrete and check_line_of_sight
+    (pure functions of the grid) so that each call is asked again under the
+    default thresholds 74 / 70 and the differing verdicts are counted: a
+    thresholds fixture must hold some. Returns the function that unwraps."""
+    saved = []
+
+    def under_defaults(mod, ship, fn, *args):
+        keep = ship.grid_threshold, mod.EW_THRESHOLD
+        ship.grid_threshold, mod.EW_THRESHOLD = 74, 70
+        try:
+            with quiet():
+                return fn(ship, *args)
+        finally:
+            ship.grid_threshold, mod.EW_THRESHOLD = keep
+
+    for mod, cls in ((combatant, combatant.Combatant), (landingship, landingship.LandingShip)):
+        move, los = cls.continuous_to_discrete, cls.check_line_of_sight
+        saved.append((cls, move, los))
+
+        def move_w(self, action, _m=move, _mod=mod):
+            res = _m(self, action)
+            counts["moves"] += 1
+            counts["moves_differ"] += (res is False) != (under_defaults(_mod, self, _m, action) is False)
+            return res
+
+        def los_w(self, origin, destination, sensor, _l=los, _mod=mod):
+            res = _l(self, origin, destination, sensor)
+            if sensor != "radar":
+                counts["ew_rays"] += 1
+                counts["ew_differ"] += bool(res) != bool(under_defaults(_mod, self, _l, origin, destination, sensor))
+            return res
+        cls.continuous_to_discrete, cls.check_line_of_sight = move_w, los_w
+
+    def unwrap():
+        for cls, move, los in saved:
+            cls.continuous_to_discrete, cls.check_line_of_sight = move, los
+    return unwrap
+
+
+LZ = (14, 82)
+
+
+def steer_to_zone(ships, act):
+    """Every landing ship's move columns head for its landing zone: the cell
+    within its speed of 2 that is nearest the zone. continuous_to_discrete
+    takes cos / sin of degrees(2 pi a2) as if it were radians (landingship.py:
+    466-478), so a2 = theta / 360 heads theta and a3 = distance / speed."""
+    for a, sh in enumerate(ships):
+        if sh.ship_type != "ls":
+            continue
+        x, y = sh.position
+        best = min(((dx, dy) for dx in range(-2, 3) for dy in range(-2, 3) if dx * dx + dy * dy <= 4),
+                   key=lambda d: ((x + d[0] - LZ[0]) ** 2 + (y + d[1] - LZ[1]) ** 2, d))
+        theta = math.atan2(best[1], best[0]) % (2 * math.pi)
+        act[a, 2], act[a, 3] = theta / 360.0, math.hypot(*best) / 2.0
+        a2, a3 = act[a, 2], act[a, 3]
+        got = (round(x + math.cos(math.degrees(2 * math.pi * a2)) * 2 * a3),
+               round(y + math.sin(math.degrees(2 * math.pi * a2)) * 2 * a3))
+        assert got == (x + best[0], y + best[1]), (got, best)
+
+
+def spawn_landed(ep, grid, rng):
+    """3 small v large + 2 ls: the first landing ship 3-5 cells from the zone, the
+    second 9-12 cells (still afloat when the first lands), the large ship
+    beside them. Even episodes: blue out of every sensor's reach (x >= 62);
+    odd episodes: blue 5-12 cells from the zone, in contact."""
+    def ring(lo, hi):
+        cells = [(x, y) for x in range(14, 30) for y in range(70, 94)
+                 if grid[x, y] <= 74 and lo <= math.hypot(x - LZ[0], y - LZ[1]) <= hi]
+        return cells[int(rng.integers(0, len(cells)))]
+    red = [ring(4, 8), ring(3, 5), ring(9, 12)]
+    if ep % 2 == 0:
+        blue = _water_in_box(grid, rng, ((62, 80), (60, 85)), 3)
+    else:
+        blue = [ring(5, 12) for _ in range(3)]
+    return blue, red
+
+
+def check_landed(fx, meta, verdicts):
+    """game.py:479-485 and :283-288 are in the fixture: at least 4 episodes end by
+    landing, one of them in contact; a landing ship's reward comes from the
+    distance-0 branch (+ 100 + 100); and in one landing a second landing ship is
+    still afloat, so the loop over the remaining landing ships has two entries."""
+    landed = contact_landed = dist0 = two_afloat = 0
+    for em in meta["episodes"]:
+        i = em["first_step"] + em["n_steps"] - 1
+        ls = [a for a, t in enumerate(em["types"]) if t == TYPE_CODE["ls"]]
+        # alive is recorded after the step's removals: a ship sunk in the landing step counts as sunk
+        on = [a for a in ls if tuple(fx["pos"][i, a]) == LZ and (i == em["first_step"] or fx["alive"][i - 1, a])]
+        if fx["done"][i] == 0 and on:
+            landed += 1
+            contact_landed += em["ep"] % 2
+            dist0 += any(fx["rew_red"][i, a - em["nb"]] >= 200.0 for a in on)
+            afloat = [a for a in ls if a not in on and fx["alive"][i, a]]
+            two_afloat += bool(afloat)
+    print(f"  landed {landed} (in contact {contact_landed}), distance-0 rewards {dist0}, "
+          f"with a second landing ship afloat {two_afloat}")
+    assert landed >= 4 and contact_landed >= 1 and dist0 >= 1 and two_afloat >= 1
+
+
+def spawn_defensive(ep, grid, rng):
+    """Even episodes: blue on the reference spawns, the reds at x 48..59 (the
+    zone of game.py:260 ends at x = 55), out of sensor reach; odd episodes: the
+    melee boxes, one inside the zone and two across its edges."""
+    if ep % 2 == 0:
+        return REF_BLUE, _water_in_box(grid, rng, ((48, 60), (42, 72)), 4)
+    box = MELEE_BOXES[(ep // 2) % len(MELEE_BOXES)]
+    return _water_in_box(grid, rng, box, 4), _water_in_box(grid, rng, box, 4)
+
+
+def check_defensive(fx, meta, verdicts):
+    nb = meta["episodes"][0]["nb"]
+    late = fx["steps_done"][:, nb:] > 14
+    x, y = fx["pos"][:, nb:, 0], fx["pos"][:, nb:, 1]
+    inside = (x >= 19) & (x <= 55) & (y >= 40) & (y <= 70)
+    n_in, n_out = int((late & inside).sum()), int((late & ~inside).sum())
+    losses = int((np.diff(fx["n_left"], axis=0) < 0).sum())
+    print(f"  ship-steps after step 14: inside {n_in}, outside {n_out}; steps with losses {losses}")
+    assert n_in >= 10 and n_out >= 10 and losses >= 3
+
+
+def _line_max(grid, x1, y1, x2, y2):
+    """The largest terrain value on the cells a sensor ray from (x1, y1) to
+    (x2, y2) visits (a Bresenham walk, error term dx - dy)."""
+    dx, dy = abs(x2 - x1), abs(y2 - y1)
+    sx, sy = (-1 if x1 > x2 else 1), (-1 if y1 > y2 else 1)
+    err, m = dx - dy, 0
+    while True:
+        m = max(m, int(grid[x1, y1]))
+        if (x1, y1) == (x2, y2):
+            return m
+        e2 = 2 * err
+        if e2 > -dy:
+            err -= dy
+            x1 += sx
+        if e2 < dx:
+            err += dx
+            y1 += sy
+
+
+def spawn_coast(ep, grid, rng):
+    """The lead ships of both sides 4-10 cells apart on open water (<= 60) across
+    shallows of 61..70: their radar ray passes, their EW ray is blocked under
+    EW_THRESHOLD 60 and passes under 70. The other ships stand on water within
+    4 cells of their lead."""
+    soft = np.argwhere((grid[:100, :100] > 60) & (grid[:100, :100] <= 70))
+    while True:
+        cx, cy = (int(v) for v in soft[int(rng.integers(0, len(soft)))])
+        dx, dy = (int(v) for v in rng.integers(-5, 6, 2))
+        a, b = (cx + dx, cy + dy), (cx - dx, cy - dy)
+        if not (4 <= math.hypot(2 * dx, 2 * dy) <= 10 and all(3 <= v < 97 for v in a + b)):
+            continue
+        if grid[a] > 60 or grid[b] > 60 or not 60 < _line_max(grid, *a, *b) <= 70:
+            continue
+        near = lambda c: _water_in_box(grid, rng, ((c[0] - 3, c[0] + 4), (c[1] - 3, c[1] + 4)), 3)  # noqa: E731
+        return [a] + near(a), [b] + near(b)
+
+
+def steer_slow(ships, act):
+    """Every ship moves at most one cell a step, so the fleets stay at the shore."""
+    act[:, 3] *= 0.3
+
+
+def check_thresholds(fx, meta, verdicts):
+    print("  threshold verdicts", verdicts)
+    assert verdicts["moves_differ"] >= 1 and verdicts["ew_differ"] >= 1
+
+
+def check_aggression(fx, meta, verdicts):
+    nb = meta["episodes"][0]["nb"]
+    alive_before = np.concatenate([np.ones_like(fx["alive"][:1]), fx["alive"][:-1]])[:, nb:] != 0
+    first = np.array([em["first_step"] for em in meta["episodes"]])
+    alive_before[first] = True
+    fired = (fx["actions_after"][:, nb:, 1] != fx["actions"][:, nb:, 1]) & alive_before
+    held = ~fired & alive_before
+    print(f"  aggression {meta['flags']['RED_AGGRESSION']}: draws fired {int(fired.sum())}, held {int(held.sum())}")
+    assert fired.sum() >= 5 and held.sum() >= 5
+
+
 def run_scenario(game, combatant, landingship, name, grids, *, nb_types, nr_types,
                  spawn="ref", n_ep=4, steps=40, flags=None, dtype="f64",
                  act_lo=0.0, act_hi=1.0, observe=False, grid_id=0, seed=0,
-                 random_ls=0, mixed_rows=False, analytics=False, list_rows=False):
+                 random_ls=0, mixed_rows=False, analytics=False, list_rows=False, steer=None,
+                 check=None):
+    """spawn: "ref", "split", "melee", or a function (ep, grid, rng) -> (blue
+    cells, red cells). steer: a function (ships, act) that overwrites action
+    rows before the step (act [A, 4] float64, ships in slot order). check: a
+    function (fixture arrays, threshold verdict counts) that asserts what the
+    fixture is there for, before it is written.
+    flags MOVEMENT_THRESHOLD / EW_THRESHOLD (combatant.py:33-34, landingship.py:
+    33-34) are recorded only where given: the default is 74 / 70."""
     if ONLY_SCENARIOS and name not in ONLY_SCENARIOS:
         return
     flags = dict(flags or {})
     F = dict(DISCRETE=False, LANDING_OPS=False, TACTICS="aggressive", SIDE="blue",
              TRAINED_RED=True, RED_AGGRESSION=0.4, N_RED_LANDINGSHIP=random_ls)
     F.update(flags)
+    # the ships read the module globals when they are built (combatant.py:87-88)
+    # and check_line_of_sight's EW branch when it is called (:453)
+    thr = (F.get("MOVEMENT_THRESHOLD", 74), F.get("EW_THRESHOLD", 70))
+    for mod in (combatant, landingship):
+        mod.MOVEMENT_THRESHOLD, mod.EW_THRESHOLD = thr
+    verdicts = dict(moves=0, moves_differ=0, ew_rays=0, ew_differ=0)
+    unwrap = _count_threshold_verdicts(combatant, landingship, verdicts) if thr != (74, 70) else None
     game.RED_AGGRESSION = F["RED_AGGRESSION"]
     game.N_RED_LANDINGSHIP = F["N_RED_LANDINGSHIP"]
     game.SIDE = F["SIDE"]
@@ -409,7 +605,9 @@ def run_scenario(game, combatant, landingship, name, grids, *, nb_types, nr_type
             env = game.Game()
             tape_start = len(tape.vals)
             blue, red = [], []
-            if spawn == "ref":
+            if callable(spawn):
+                bpos, rpos = spawn(ep, grid, rng)
+            elif spawn == "ref":
                 bpos = REF_BLUE[:nb]
                 rpos = REF_RED4[:nr0]
             elif spawn == "split":
@@ -491,6 +689,10 @@ def run_scenario(game, combatant, landingship, name, grids, *, nb_types, nr_type
                     else:
                         call_act = act.copy()
                         row_f32 = np.zeros(A, np.uint8)
+                if steer is not None:
+                    assert dtype == "f64" and not mixed_rows and not F["DISCRETE"]
+                    steer(ships_all, act)
+                    call_act = act.copy()
                 rec["actions"].append(np.asarray(act, dtype=np.float64))
                 rec["row_f32"].append(row_f32)
                 ret, cap = _capture_step(game, env, call_act)
@@ -542,6 +744,10 @@ def run_scenario(game, combatant, landingship, name, grids, *, nb_types, nr_type
         print("  crash in", name, repr(exc))
     finally:
         np.random.beta = np_beta
+        if unwrap:
+            unwrap()
+        for mod in (combatant, landingship):
+            mod.MOVEMENT_THRESHOLD, mod.EW_THRESHOLD = 74, 70
 
     # drop a partially recorded (crashed) episode
     n_ok = sum(m["n_steps"] for m in ep_meta if "n_steps" in m)
@@ -590,6 +796,8 @@ def run_scenario(game, combatant, landingship, name, grids, *, nb_types, nr_type
         out.update(pre_obs=np.array(rec["pre_obs"], np.float32),
                    pre_obs_valid=np.array(rec["pre_obs_valid"], np.uint8),
                    pre_tl_cnt=ptl_cnt, pre_tl_xy=ptl_xy)
+    if check is not None:
+        check(out, meta_all, verdicts)
     np.savez_compressed(os.path.join(OUT, f"ep_{name}.npz"), **out)
     print(f"episode fixture {name}: {len(ep_meta)} episodes, {n_ok} steps, "
           f"{len(tape.vals)} draws, crashes={crashes}")
@@ -655,6 +863,42 @@ def make_episodes(game, combatant, landingship, grids, quick):
                  nr_types=M, spawn="melee", n_ep=q(6), seed=24, flags=dict(DISCRETE=True))
     run_scenario(game, combatant, landingship, "3v3_medium_untrained_red", grids, nb_types=M[:3],
                  nr_types=M[:3], spawn="melee", n_ep=q(6), seed=25, flags=dict(TRAINED_RED=False))
+    make_option_episodes(game, combatant, landingship, grids)
+
+
+def make_option_episodes(game, combatant, landingship, grids):
+    """The scenario options that the fixtures above leave at their defaults or
+    never bring to their branch: episodes of at most 25 steps, each fixture
+    checked for what it is there for before it is written (check_*)."""
+    S4, R4 = ["small"] * 4, ["large"] * 4
+    run = lambda name, **kw: run_scenario(game, combatant, landingship, name, grids, steps=25, **kw)  # noqa: E731
+    # the landing ending (game.py:479-485: done, blue rewards zeroed, red + 100,
+    # blue_victory incremented) and calculate_reward's distance-0 branch
+    # (game.py:283-288). The landing ships are steered (steer_to_zone), every other
+    # row is random; seed 31 is the first of 31.. whose episodes meet check_landed.
+    run("3v2ls_landed", nb_types=S4[:3], nr_types=["large", "ls", "ls"], spawn=spawn_landed, n_ep=8,
+        seed=31, flags=dict(LANDING_OPS=True), steer=steer_to_zone, check=check_landed)
+    # the defensive zone reward after step 14 (game.py:258-263), the neutralised
+    # penalty and the zeroing at victory (game.py:435-454)
+    run("4v4_defensive_zone", nb_types=S4, nr_types=R4, spawn=spawn_defensive, n_ep=6, seed=32,
+        flags=dict(TACTICS="defensive"), check=check_defensive)
+    run("4v4_defensive_zone_untrained", nb_types=S4, nr_types=R4, spawn=spawn_defensive, n_ep=6, seed=33,
+        flags=dict(TACTICS="defensive", TRAINED_RED=False), check=check_defensive)
+    # movement threshold above and EW threshold below the defaults 74 / 70: cells
+    # of 75..85 admit a move and pass a radar ray, cells of 61..70 block an EW ray.
+    # (The other way round no EW verdict can differ: get_obs asks for the EW ray
+    # only where the radar ray, under the movement threshold, has passed,
+    # combatant.py:110-119, so an EW threshold above it decides nothing.)
+    run("4v4_thresholds", nb_types=S4, nr_types=R4, spawn=spawn_coast, n_ep=6, seed=34,
+        flags=dict(MOVEMENT_THRESHOLD=85, EW_THRESHOLD=60), steer=steer_slow, check=check_thresholds)
+    # the scripted red's salvo draw (game.py:377-379) nearly always and nearly never
+    run("4v4_aggression_hi", nb_types=S4, nr_types=R4, spawn="melee", n_ep=8, seed=35,
+        flags=dict(TRAINED_RED=False, RED_AGGRESSION=0.9), check=check_aggression)
+    run("4v4_aggression_lo", nb_types=S4, nr_types=R4, spawn="melee", n_ep=8, seed=36,
+        flags=dict(TRAINED_RED=False, RED_AGGRESSION=0.05), check=check_aggression)
+    # the learner plays red (game.py:330-358, 522-525) with landing ops
+    run("3v2ls_side_red", nb_types=S4[:3], nr_types=["large", "large", "ls"], spawn="melee", n_ep=6,
+        seed=37, flags=dict(SIDE="red", LANDING_OPS=True))
 
 
 def main():
@@ -676,6 +920,8 @@ def main():
         make_astar(game, combatant, g100, g200, quick)
     if not only or "episodes" in only:
         make_episodes(game, combatant, landingship, grids, quick)
+    elif "options" in only:
+        make_option_episodes(game, combatant, landingship, grids)
     if "--analytics" in sys.argv or "analytics" in only:
         make_analytics_episodes(game, combatant, landingship, grids, quick)
 

@@ -105,7 +105,9 @@ def replay_oracle(fx, grids):
         nb, nr = em["nb"], em["nr"]
         env = OracleEnv(grid, nb, nr, discrete=F["DISCRETE"], landing_ops=F["LANDING_OPS"],
                         aggressive=F["TACTICS"] == "aggressive", side_blue=F["SIDE"] == "blue",
-                        trained_red=F["TRAINED_RED"], red_aggression=F["RED_AGGRESSION"])
+                        trained_red=F["TRAINED_RED"], red_aggression=F["RED_AGGRESSION"],
+                        move_thr=F.get("MOVEMENT_THRESHOLD", 74), ew_thr=F.get("EW_THRESHOLD", 70),
+                        lz=tuple(meta.get("landing_zone", (14, 82))))
         tape = fx["tape"][em["tape_start"]:em["tape_end"]]
         env.set_tape(tape)
         types = np.array(em["types"], np.int32)
