@@ -716,7 +716,8 @@ int lnw_ppo_clip_adam(float *params, const float *grad, float *m, float *v, int6
  * drawn only after every finite row, in row order. The key depends on the global
  * row alone, so the first `batch` of the union of two shards' (key_out, row_base
  * + index_out), merged by (key, global row), is what one call over all rows
- * draws.
+ * draws. lnw_ppo_sample_merge below is that merge on the device, for any number
+ * of shards up to 64.
  * The call's last launch gathers actions, log_probs [rows][4], rtg and values[r
  * / n] of the drawn rows (each where both its input and its output are given)
  * and, with advance, adds 1 to *draw_dev.
@@ -746,6 +747,81 @@ typedef struct lnw_ppo_sample_args {
 } lnw_ppo_sample_args;
 int64_t lnw_ppo_sample_workspace_bytes(int64_t rows, int64_t batch);  /* 0: unsupported */
 int lnw_ppo_sample(const lnw_ppo_sample_args *args, void *stream);
+
+/* ---- Training over sharded rollouts ---------------------------------------------
+ * Every rank draws `batch` candidates from its own rows (lnw_ppo_sample with its
+ * row_base), the ranks exchange the candidate lists, every rank merges them into
+ * the one draw over all rows, packs the payload of the slots whose rows it owns,
+ * and the packed buffers are summed over the ranks: every rank then holds the
+ * same minibatch and runs lnw_ppo_grad / lnw_ppo_clip_adam on it. The collectives
+ * are the caller's (lnw/ppodist.py: one all-gather, one integer all-reduce).
+ *
+ * lnw_ppo_sample_merge: lists [W][stride] int64, stride >= 2 batch + 1, list w is
+ * rank w's message: words [0, batch) the bits of its key_out (float64), words
+ * [batch, 2 batch) its global rows row_base + index_out, word 2 batch its status
+ * count. Each list is ascending in (key, global row), as lnw_ppo_sample leaves it;
+ * keys are non-negative (a zero key is +0, a non-finite row +inf), global rows
+ * are < 2^40 and distinct across the lists. For slot s in [0, batch) the call
+ * writes the s-th element of the union of the lists in the total order (key as a
+ * number, global row as a 64-bit value):
+ *   key_out[s], row_out[s]           its key and global row
+ *   src_rank[s], src_pos[s]          the list it came from and its place there
+ *   index_out[s] = s n + row_out[s] % n   its row of lnw_ppo_rows_pack's xobs
+ *   status_out[0]                    the sum of the W status words
+ * One thread per candidate: its place in the union is its place in its own list
+ * plus, for every other list, the number of elements before it (binary search).
+ * One launch on `stream`: no host synchronisation, no allocation, no workspace,
+ * no atomics, every output written by exactly one thread: bitwise reproducible.
+ * 1 <= W <= 64 and 1 <= batch <= LNW_SAMPLE_MAX_BATCH (else LNW_EUNSUPPORTED);
+ * n >= 1; int64 / double arrays 8-B aligned. With W = 1 the call copies the list. */
+typedef struct lnw_ppo_merge_args {
+  const int64_t *lists;        /* [W][stride] */
+  int32_t W, n;
+  int64_t stride, batch;
+  double *key_out;             /* [batch] */
+  int64_t *row_out;            /* [batch] global rows */
+  int32_t *src_rank, *src_pos; /* [batch] */
+  int64_t *index_out;          /* [batch] */
+  int64_t *status_out;         /* [1] */
+} lnw_ppo_merge_args;
+int lnw_ppo_sample_merge(const lnw_ppo_merge_args *args, void *stream);
+
+/* lnw_ppo_rows_pack writes the exchange buffer of rank `rank`, whose rows are the
+ * global rows [row_base, row_base + rows): xbuf, 32-bit words, every region
+ * starting on a 16-B boundary, in this order:
+ *   xobs          [batch][n][D]
+ *   actions       [batch][4]
+ *   old_log_probs [batch][4]
+ *   rtg           [batch], padded to a multiple of 4 words
+ *   old_values    [batch], padded to a multiple of 4 words
+ * lnw_ppo_pack_words(batch, n, D) words in all (0 for unsupported shapes). Slot s
+ * with src_rank[s] == rank and local row r = row_out[s] - row_base holds the n D
+ * floats of the row's group obs[r / n] (read in place, as float4), actions[r],
+ * log_probs[r], rtg[r] and values[r / n], bit for bit; every other slot, and the
+ * padding, is zero words. Every word of xbuf is written on every call. Summed
+ * over the ranks as int32, the buffers give every rank each owner's bits (a
+ * float sum would lose -0.0 and NaN payloads), and xobs with lnw_ppo_sample_merge's
+ * index_out is lnw_ppo_grad's obs / row_index.
+ * Two launches on `stream`: no host synchronisation, no allocation, no atomics;
+ * bitwise reproducible. Width limits are lnw_ppo_grad's (D % 4 == 0, 49 <= D, D -
+ * 37 <= 64, 1 <= n <= 16) and 1 <= batch <= LNW_SAMPLE_MAX_BATCH, else
+ * LNW_EUNSUPPORTED; rows % n == 0, row_base % n == 0, 0 <= rank < 64, row_base +
+ * rows <= 2^40; obs, actions, log_probs and xbuf 16-B aligned. */
+typedef struct lnw_ppo_pack_args {
+  const float *obs;            /* [rows / n][n][D], 16-B aligned */
+  const float *actions, *log_probs;  /* [rows][4], 16-B aligned */
+  const float *rtg;            /* [rows] */
+  const float *values;         /* [rows / n] */
+  int64_t rows, row_base;
+  int32_t n, D, rank;
+  int64_t batch;
+  const int64_t *row_out;      /* [batch] lnw_ppo_sample_merge's */
+  const int32_t *src_rank;     /* [batch] */
+  uint32_t *xbuf;              /* [xbuf_words] out, 16-B aligned */
+  int64_t xbuf_words;          /* >= lnw_ppo_pack_words(batch, n, D) */
+} lnw_ppo_pack_args;
+int64_t lnw_ppo_pack_words(int64_t batch, int32_t n, int32_t D);  /* 0: unsupported */
+int lnw_ppo_rows_pack(const lnw_ppo_pack_args *args, void *stream);
 
 /* Host-side constants the kernels use (for tests): hit probability tables
  * 1-(1-p)^n for p in {0.45, 0.63}, n = 0..8, in float64 and float32. */

@@ -36,6 +36,7 @@ SYMBOLS = [
     "lnw_ppolearn_workspace_bytes", "lnw_ppo_grad", "lnw_ppo_clip_adam",
     "lnw_policy_packed_floats", "lnw_actor_perturb", "lnw_policy_act_pop",
     "lnw_ppo_sample_workspace_bytes", "lnw_ppo_sample",
+    "lnw_ppo_sample_merge", "lnw_ppo_pack_words", "lnw_ppo_rows_pack",
 ]
 # lnw_ppo_sample's Philox counter words 2 and 3, and its largest batch (include/lnw.h)
 LNW_SAMPLE_CTR2, LNW_SAMPLE_CTR3, LNW_SAMPLE_MAX_BATCH = 0x13198A2E, 0x03707344, 131072
@@ -155,6 +156,21 @@ class PpoSampleArgs(C.Structure):  # include/lnw.h: lnw_ppo_sample_args
                 ("status", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+class PpoMergeArgs(C.Structure):  # include/lnw.h: lnw_ppo_merge_args
+    _fields_ = [("lists", C.c_void_p), ("W", C.c_int32), ("n", C.c_int32), ("stride", C.c_int64),
+                ("batch", C.c_int64), ("key_out", C.c_void_p), ("row_out", C.c_void_p),
+                ("src_rank", C.c_void_p), ("src_pos", C.c_void_p), ("index_out", C.c_void_p),
+                ("status_out", C.c_void_p)]
+
+
+class PpoPackArgs(C.Structure):  # include/lnw.h: lnw_ppo_pack_args
+    _fields_ = [("obs", C.c_void_p), ("actions", C.c_void_p), ("log_probs", C.c_void_p), ("rtg", C.c_void_p),
+                ("values", C.c_void_p), ("rows", C.c_int64), ("row_base", C.c_int64),
+                ("n", C.c_int32), ("D", C.c_int32), ("rank", C.c_int32), ("batch", C.c_int64),
+                ("row_out", C.c_void_p), ("src_rank", C.c_void_p), ("xbuf", C.c_void_p),
+                ("xbuf_words", C.c_int64)]
+
+
 class LnwError(RuntimeError):
     pass
 
@@ -222,6 +238,9 @@ def load(path=None):
         "lnw_policy_act_pop": ([C.POINTER(PolicyArgs), C.POINTER(PolicyPop), P], C.c_int),
         "lnw_ppo_sample_workspace_bytes": ([I64, I64], C.c_int64),
         "lnw_ppo_sample": ([C.POINTER(PpoSampleArgs), P], C.c_int),
+        "lnw_ppo_sample_merge": ([C.POINTER(PpoMergeArgs), P], C.c_int),
+        "lnw_ppo_pack_words": ([I64, I32, I32], C.c_int64),
+        "lnw_ppo_rows_pack": ([C.POINTER(PpoPackArgs), P], C.c_int),
     }
     for name, (args, res) in sig.items():
         # (a library built before an additive getter existed still loads, for

@@ -1,7 +1,8 @@
 """One process per GPU. Environments shard by global id (lnw.shard); the step
 has no collective. Collectives are used only off the step path: the bench's
 max-over-ranks wall time and optional episode-counter sums (RCCL all_reduce
-over xGMI on the GPU box, gloo on CPU)."""
+over xGMI on the GPU box, gloo on CPU), and the two exchanges of a minibatch
+drawn over sharded rollouts (all_gather, all_reduce_sum_: lnw.ppodist)."""
 import os
 
 import torch
@@ -63,6 +64,52 @@ def reduce_sum(values):
     if dist.is_initialized():
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
     return [float(v) for v in t.cpu()]
+
+
+def _staged(group):
+    """True when a collective on a device tensor has to go through the host
+    (gloo); RCCL takes the device tensor on the current stream."""
+    return dist.get_backend(group) != "nccl"
+
+
+def all_gather(t, group=None):
+    """Every rank's copy of the 1-d tensor `t`, as [world, t.numel()] on t's
+    device, rank order. "nccl": on the device tensors, on the current stream,
+    nothing synchronises with the host; "gloo": staged through the host (it
+    synchronises). No process group: t[None], a world of one."""
+    if not dist.is_initialized():
+        return t[None]
+    ws = dist.get_world_size(group)
+    if t.is_cuda and _staged(group):
+        host = t.cpu()
+        out = torch.empty(ws * host.numel(), dtype=host.dtype)
+        dist.all_gather_into_tensor(out, host, group=group)
+        return out.to(t.device).view(ws, -1)
+    out = torch.empty(ws * t.numel(), dtype=t.dtype, device=t.device)
+    dist.all_gather_into_tensor(out, t, group=group)
+    return out.view(ws, -1)
+
+
+def all_reduce_sum_(t, group=None):
+    """Element-wise sum over ranks, in place, of a tensor of any dtype the
+    backend sums (int32 for lnw.ppodist's exchange buffer); staged as
+    all_gather is. Returns t."""
+    if not dist.is_initialized():
+        return t
+    if t.is_cuda and _staged(group):
+        host = t.cpu()
+        dist.all_reduce(host, op=dist.ReduceOp.SUM, group=group)
+        t.copy_(host)
+    else:
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    return t
+
+
+def rank_size(group=None):
+    """(rank, world size) in `group`, (0, 1) with no process group."""
+    if not dist.is_initialized():
+        return 0, 1
+    return dist.get_rank(group), dist.get_world_size(group)
 
 
 def barrier():

@@ -5,8 +5,10 @@ Reference: ppo.py:673-693 (evaluate), ppo.py:695-714 (gae, over the minibatch
 rows as the sequence), ppo.py:716-729 (popart_normalize), ppo.py:342-362 (the
 two losses), ppo.py:371-380 (clip_grad_norm_ and Adam per network),
 ppo.py:311-319 (the prioritised sampler). The kernels are csrc/lnw_ppolearn.hip
-(lnw_ppo_grad, lnw_ppo_clip_adam) and csrc/lnw_pposample.hip (lnw_ppo_sample,
-the keyed minibatch draw behind PPOLearner.minibatch). learn()'s outer schedule
+(lnw_ppo_grad, lnw_ppo_clip_adam), csrc/lnw_pposample.hip (lnw_ppo_sample,
+the keyed minibatch draw behind PPOLearner.minibatch) and csrc/lnw_ppodist.hip
+(the merge and the row exchange behind PPOLearner.minibatch_dist, which trains
+on rollouts sharded over ranks: lnw/ppodist.py). learn()'s outer schedule
 (noise ratio, lr halving on victories, epoch count) and red-side training stay
 with the caller;
 parameter noise is the rollout's (lnw.rollout.Rollout(param_noise=..., theta=
@@ -226,6 +228,7 @@ class PPOLearner:
     index [B] int64 rows of obs.reshape(-1, D) or None for all rows in order,
     actions [B, 4], old_log_probs [B, 4], rtg [B], old_values [B]). minibatch()
     draws the reference's prioritised minibatch on the device (lnw_ppo_sample);
+    minibatch_dist() draws it over the rollouts of every rank of a process group;
     sample() is the same distribution through torch.multinomial."""
 
     def __init__(self, actor, critic, lr=1e-4, eps_clip=0.2, entropy_coef=0.2, gamma=0.99, lambda_=0.95,
@@ -268,6 +271,7 @@ class PPOLearner:
         self.draw = torch.zeros(1, dtype=torch.int64, device=dev)
         self.sample_status = torch.zeros(1, dtype=torch.int64, device=dev)
         self._sample_buf = {}
+        self._dist_buf = {}  # minibatch_dist(): the merge's outputs and the exchange buffer per (batch, n, D)
 
     # ---- batches -------------------------------------------------------------------
     def rows(self, out, index=None, rtg=None):
@@ -318,6 +322,23 @@ class PPOLearner:
         of the same shape overwrites. impl="torch": the same draw from the
         definition with NumPy on the host (it reads the counter, so it
         synchronises), the same index bit for bit."""
+        ro = self.rollout_rows(out, rtg)
+        N, B = ro["rtg"].shape[0], int(batch)
+        from ._abi import LNW_SAMPLE_MAX_BATCH
+        if not 1 <= B <= min(N, LNW_SAMPLE_MAX_BATCH):
+            raise ValueError(f"batch must be in 1 .. min(rows, {LNW_SAMPLE_MAX_BATCH})")
+        seed = (self.sample_seed if seed is None else int(seed)) & (2 ** 64 - 1)
+        draw = self._sample_hip if self.impl == "hip" else self._sample_torch
+        b = draw(ro["rtg"], ro["actions"], ro["log_probs"], ro["values"], ro["n"], B, seed, int(row_base),
+                 bool(advance))
+        return dict(obs=ro["obs"], index=b["index"], actions=b["actions"], old_log_probs=b["old_log_probs"],
+                    rtg=b["rtg"], old_values=b["old_values"], key=b["key"])
+
+    def rollout_rows(self, out, rtg=None):
+        """The tensors of a Rollout.run() result as the draw reads them, on the
+        learner's device, without a copy where they already are float32 and
+        contiguous: dict(obs [groups, n, D], rtg [N], actions, log_probs [N, 4],
+        values [groups], n, D), N = groups * n rows of (env, step, ship)."""
         dev = self.device
         obs = out["obs"]
         n, D = obs.shape[-2], obs.shape[-1]
@@ -326,17 +347,35 @@ class PPOLearner:
         acts = out["actions"].reshape(-1, 4).to(dev, torch.float32).contiguous()
         lps = out["log_probs"].reshape(-1, 4).to(dev, torch.float32).contiguous()
         vals = out["values"].reshape(-1).to(dev, torch.float32).contiguous()
-        N, B = rtg.shape[0], int(batch)
-        from ._abi import LNW_SAMPLE_MAX_BATCH
-        if not 1 <= B <= min(N, LNW_SAMPLE_MAX_BATCH):
-            raise ValueError(f"batch must be in 1 .. min(rows, {LNW_SAMPLE_MAX_BATCH})")
+        N = rtg.shape[0]
         if acts.shape[0] != N or lps.shape[0] != N or vals.shape[0] * n != N:
             raise ValueError("rtg, actions and log_probs need one row per (env, step, ship), values one per (env, step)")
-        seed = (self.sample_seed if seed is None else int(seed)) & (2 ** 64 - 1)
-        draw = self._sample_hip if self.impl == "hip" else self._sample_torch
-        b = draw(rtg, acts, lps, vals, n, B, seed, int(row_base), bool(advance))
-        return dict(obs=obs, index=b["index"], actions=b["actions"], old_log_probs=b["old_log_probs"], rtg=b["rtg"],
-                    old_values=b["old_values"], key=b["key"])
+        return dict(obs=obs, rtg=rtg, actions=acts, log_probs=lps, values=vals, n=n, D=D)
+
+    def minibatch_dist(self, out, batch, row_base, seed=None, rtg=None, advance=True, group=None):
+        """minibatch() over rollouts sharded across the ranks of a process group:
+        `out` holds this rank's rows, global rows [row_base, row_base + rows) of
+        the job's (row_base a multiple of n; the ranks' ranges are disjoint), and
+        every rank gets the minibatch that one minibatch() over all the rows
+        would draw, with its payload: the dict step() / grad() take, obs = the
+        drawn rows' groups packed as [batch, n, D], index their rows of it,
+        actions, old_log_probs, rtg, old_values, key, and global_row [batch]
+        int64. Same seed, counter and learner state on every rank give bitwise
+        equal results on every rank, so the ranks' step() stay equal to each
+        other and to one rank training on all rows.
+
+        Every rank draws `batch` candidates locally (batch <= its own rows, else
+        ValueError before any collective), one all-gather exchanges the
+        candidate lists, lnw_ppo_sample_merge merges them, lnw_ppo_rows_pack
+        packs the rows this rank owns, and one int32 SUM all-reduce assembles
+        the buffer (lnw.ppodist). group: the process group (None: the default
+        one; with none initialised, a world of one). On "nccl" (RCCL) nothing
+        synchronises with the host; "gloo" stages through it. self.draw advances
+        as in minibatch(); self.sample_status holds the count over all ranks.
+        The returned tensors are buffers the next call of the same shape
+        overwrites. impl="torch": the same protocol with NumPy / torch indexing."""
+        from . import ppodist
+        return ppodist.minibatch_dist(self, out, batch, row_base, seed=seed, rtg=rtg, advance=advance, group=group)
 
     def _sample_hip(self, rtg, acts, lps, vals, n, B, seed, row_base, advance):
         from . import _abi
