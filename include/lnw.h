@@ -823,6 +823,82 @@ typedef struct lnw_ppo_pack_args {
 int64_t lnw_ppo_pack_words(int64_t batch, int32_t n, int32_t D);  /* 0: unsupported */
 int lnw_ppo_rows_pack(const lnw_ppo_pack_args *args, void *stream);
 
+/* ---- DDQN replay ------------------------------------------------------------------
+ * The transitions of QCollector's ring (lnw/qlearn.py), drawn and packed on the
+ * device. The ring holds `cap` steps of E envs: state, next_state [cap][E][n][D]
+ * float32, action [cap][E][n][4] int32, reward [cap][E][n] float32 or float64,
+ * done [cap][E] int32. Beside it lies priority [E][cap] float32, env-major, so
+ * that a shard of consecutive envs is a contiguous range of the global rows:
+ *   local row  r = e cap + k            (env e of the shard, ring slot k)
+ *   global row g = row_base + r,  row_base = (the shard's first global env) cap
+ * NaN marks a slot that holds no transition yet.
+ *
+ * The draw is lnw_ppo_sample above, unchanged, with rtg = priority, rows = E cap,
+ * that row_base, n = 1 and every gather column NULL: weight |p| + 1e-5, `batch`
+ * distinct transitions in ascending (key, global row) order, a NaN entry drawn
+ * only after every real one and counted in status. Equal priorities make it
+ * uniform sampling without replacement (random.sample, ddqn.py:74-76). Shards
+ * merge with lnw_ppo_sample_merge (n = 1). Its limits hold: E cap < 2^31,
+ * row_base + E cap <= 2^40.
+ *
+ * lnw_replay_mark writes priority[e][k] for every env e after a collector step
+ * has filled ring slot k: 1.0f when reward is NULL, else the sum over ships i =
+ * 0 .. n-1, in that order, in float32, of fabsf((float)reward[k][e][i]). One
+ * launch on `stream`; 0 <= k < cap, 1 <= n <= 16. */
+typedef struct lnw_replay_mark_args {
+  float *priority;             /* [E][cap] */
+  const void *reward;          /* NULL (priority 1), or [cap][E][n] float32 / float64 */
+  int32_t reward_f64;
+  int32_t n, cap, k;
+  int64_t E;
+} lnw_replay_mark_args;
+int lnw_replay_mark(const lnw_replay_mark_args *args, void *stream);
+
+/* lnw_replay_pack writes the drawn transitions as lnw_qnet_grad's row tensors into
+ * xbuf, 32-bit words, every region starting on a 16-B boundary, in this order:
+ *   state      [batch][n][D]
+ *   next_state [batch][n][D]
+ *   action     [batch][n][4]
+ *   reward     [batch][n], one word each, or two with reward_f64; padded to a
+ *              multiple of 4 words
+ *   done       [batch][n], the ring's done[k][e] repeated for each ship; padded
+ *              likewise
+ * lnw_replay_pack_words(batch, n, D, reward_f64) words in all (0 for unsupported
+ * shapes). Slot s is owned when src_rank is NULL or src_rank[s] == rank. An owned
+ * slot with local row r = row_out[s] - row_base in [0, E cap), e = r / cap, k = r
+ * % cap, holds that transition's words bit for bit (-0.0, NaN payloads and
+ * denormals kept). Every slot that is not owned, every owned slot whose r lies
+ * outside that range (nothing is read out of range), and all padding are zero
+ * words. Every word of xbuf is written on every call. With src_rank NULL the call
+ * is the local gather; with lnw_ppo_sample_merge's row_out / src_rank it writes a
+ * rank's exchange buffer, and the ranks' buffers summed as int32 give every rank
+ * each owner's bits. index_out, if given, receives k E + e per slot (the ring's
+ * flat (step, env) index, QCollector.sample()'s convention), -1 for a slot that
+ * holds zero words.
+ * One launch on `stream`, one thread per 16 B of xbuf (float4 accesses, 64-bit
+ * ring offsets): no host synchronisation, no allocation, no workspace, no
+ * atomics; bitwise reproducible. D % 4 == 0, 49 <= D <= 101, 1 <= n <= 16, 1 <=
+ * batch <= LNW_SAMPLE_MAX_BATCH, 0 <= rank < 64, else LNW_EUNSUPPORTED; state,
+ * next_state, action and xbuf 16-B aligned. */
+typedef struct lnw_replay_pack_args {
+  const float *state, *next_state;  /* [cap][E][n][D], 16-B aligned */
+  const int32_t *action;       /* [cap][E][n][4], 16-B aligned */
+  const void *reward;          /* [cap][E][n] float32, or float64 with reward_f64 */
+  const int32_t *done;         /* [cap][E] */
+  int32_t reward_f64;
+  int32_t cap, n, D;
+  int64_t E;
+  int64_t row_base, batch;
+  const int64_t *row_out;      /* [batch] global rows */
+  const int32_t *src_rank;     /* NULL (every slot owned), or [batch] */
+  int32_t rank;
+  int64_t *index_out;          /* NULL, or [batch] */
+  uint32_t *xbuf;              /* [xbuf_words] out, 16-B aligned */
+  int64_t xbuf_words;          /* >= lnw_replay_pack_words(batch, n, D, reward_f64) */
+} lnw_replay_pack_args;
+int64_t lnw_replay_pack_words(int64_t batch, int32_t n, int32_t D, int32_t reward_f64);  /* 0: unsupported */
+int lnw_replay_pack(const lnw_replay_pack_args *args, void *stream);
+
 /* Host-side constants the kernels use (for tests): hit probability tables
  * 1-(1-p)^n for p in {0.45, 0.63}, n = 0..8, in float64 and float32. */
 int lnw_hit_tables(double *tab64 /* [2][9] */, float *tab32 /* [2][9] */);

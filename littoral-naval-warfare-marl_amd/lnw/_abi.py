@@ -37,6 +37,7 @@ SYMBOLS = [
     "lnw_policy_packed_floats", "lnw_actor_perturb", "lnw_policy_act_pop",
     "lnw_ppo_sample_workspace_bytes", "lnw_ppo_sample",
     "lnw_ppo_sample_merge", "lnw_ppo_pack_words", "lnw_ppo_rows_pack",
+    "lnw_replay_mark", "lnw_replay_pack_words", "lnw_replay_pack",
 ]
 # lnw_ppo_sample's Philox counter words 2 and 3, and its largest batch (include/lnw.h)
 LNW_SAMPLE_CTR2, LNW_SAMPLE_CTR3, LNW_SAMPLE_MAX_BATCH = 0x13198A2E, 0x03707344, 131072
@@ -171,6 +172,19 @@ class PpoPackArgs(C.Structure):  # include/lnw.h: lnw_ppo_pack_args
                 ("xbuf_words", C.c_int64)]
 
 
+class ReplayMarkArgs(C.Structure):  # include/lnw.h: lnw_replay_mark_args
+    _fields_ = [("priority", C.c_void_p), ("reward", C.c_void_p), ("reward_f64", C.c_int32), ("n", C.c_int32),
+                ("cap", C.c_int32), ("k", C.c_int32), ("E", C.c_int64)]
+
+
+class ReplayPackArgs(C.Structure):  # include/lnw.h: lnw_replay_pack_args
+    _fields_ = [("state", C.c_void_p), ("next_state", C.c_void_p), ("action", C.c_void_p), ("reward", C.c_void_p),
+                ("done", C.c_void_p), ("reward_f64", C.c_int32), ("cap", C.c_int32), ("n", C.c_int32),
+                ("D", C.c_int32), ("E", C.c_int64), ("row_base", C.c_int64), ("batch", C.c_int64),
+                ("row_out", C.c_void_p), ("src_rank", C.c_void_p), ("rank", C.c_int32), ("index_out", C.c_void_p),
+                ("xbuf", C.c_void_p), ("xbuf_words", C.c_int64)]
+
+
 class LnwError(RuntimeError):
     pass
 
@@ -241,6 +255,9 @@ def load(path=None):
         "lnw_ppo_sample_merge": ([C.POINTER(PpoMergeArgs), P], C.c_int),
         "lnw_ppo_pack_words": ([I64, I32, I32], C.c_int64),
         "lnw_ppo_rows_pack": ([C.POINTER(PpoPackArgs), P], C.c_int),
+        "lnw_replay_mark": ([C.POINTER(ReplayMarkArgs), P], C.c_int),
+        "lnw_replay_pack_words": ([I64, I32, I32, I32], C.c_int64),
+        "lnw_replay_pack": ([C.POINTER(ReplayPackArgs), P], C.c_int),
     }
     for name, (args, res) in sig.items():
         # (a library built before an additive getter existed still loads, for

@@ -21,7 +21,8 @@ DIAG_DEFINES = ("LNW_DIAG", "LNW_GROUP_PROF")
 SOURCES = [os.path.join(CSRC, "lnw_kernels.hip"), os.path.join(CSRC, "lnw_actor.hip"),
            os.path.join(CSRC, "lnw_qnet.hip"), os.path.join(CSRC, "lnw_qlearn.hip"),
            os.path.join(CSRC, "lnw_ppolearn.hip"), os.path.join(CSRC, "lnw_actornoise.hip"),
-           os.path.join(CSRC, "lnw_pposample.hip"), os.path.join(CSRC, "lnw_ppodist.hip")]
+           os.path.join(CSRC, "lnw_pposample.hip"), os.path.join(CSRC, "lnw_ppodist.hip"),
+           os.path.join(CSRC, "lnw_replay.hip")]
 # everything a source can include: csrc's own files and the C-ABI header
 # (csrc/ holds library sources only: a stray file there changes source_digest())
 DEPS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC)

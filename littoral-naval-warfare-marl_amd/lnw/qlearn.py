@@ -6,7 +6,9 @@ collector that fills a device replay ring. Observations never leave the GPU.
 Reference: network.py:246-305 (DMLP), ddqn.py:149-151 (get_epsilon),
 ddqn.py:286-387 (acting), ddqn.py:153-247 (optimize(): QLearner, the TD loss,
 its gradient and the clamped Adam step as HIP kernels, csrc/lnw_qlearn.hip).
-Replay prioritisation stays with the caller.
+QCollector.minibatch / minibatch_dist draw the replay minibatch on the device,
+without replacement, uniformly or by priorities kept beside the ring
+(lnw/replay.py, csrc/lnw_replay.hip).
 """
 import ctypes as C
 import math
@@ -309,10 +311,27 @@ class QCollector:
     Draws are keyed by (seed, step, side, global row): kernel slot 2 * step +
     (0 blue, 1 red), `step` advancing once per step(), so two collectors with
     equal seeds over equal games fill equal rings, however the envs are sharded.
+
+    priority: None — the collector above and nothing more (minibatch() raises).
+    "uniform" or "reward" — `priority`, a float32 [E, cap] device tensor beside
+    the ring (env-major: local row e * cap + k for ring slot k, global row
+    (env_id_base + e) * cap + k; NaN while the slot holds no transition), which
+    one lnw_replay_mark launch per step() fills for the slot just written: 1.0,
+    or the float32 sum over the ships of |reward|. minibatch() and
+    minibatch_dist() draw from it with lnw_ppo_sample's keyed draw without
+    replacement (weights |p| + 1e-5; equal priorities are uniform sampling
+    without replacement, the reference's random.sample, ddqn.py:74-76). The
+    tensor is public and is read at draw time: a caller may rewrite entries in
+    place with any finite values, for example TD errors from QLearner.grad's
+    `y` and `qs`. `draw` (int64 [1]) is the draw counter on the device,
+    `sample_status` (int64 [1]) the last draw's count of non-finite priorities,
+    E * (cap - filled) unless the caller planted some; sample_seed the default
+    seed of the draws; impl "hip" (the kernels) or "torch" (lnw/replay.py's
+    restatement, the same bits).
     """
 
     def __init__(self, game: BatchedGame, blue_net, red="random", capacity=64, seed=0, side="blue",
-                 bn="sample"):
+                 bn="sample", priority=None, sample_seed=0, impl="hip"):
         if not game.sc.discrete:
             raise ValueError("QCollector needs a DISCRETE BatchedGame (Scenario(discrete=True))")
         if side not in ("blue", "red"):
@@ -321,6 +340,10 @@ class QCollector:
             raise ValueError("red must be 'random', a BatchedQNet or None")
         if side == "red" and not isinstance(red, BatchedQNet):
             raise ValueError("side='red' needs a red BatchedQNet")
+        if priority not in (None, "uniform", "reward"):
+            raise ValueError("priority must be None, 'uniform' or 'reward'")
+        if impl not in ("hip", "torch"):
+            raise ValueError("impl must be 'hip' or 'torch'")
         g = self.g = game
         self.blue_net, self.red, self.side, self.bn = blue_net, red, side, bn
         self.cap, self.seed = int(capacity), int(seed)
@@ -335,6 +358,14 @@ class QCollector:
         self.steps = 0      # steps taken (slot of the keyed draws, ring position)
         self.t = 0          # episode step of untrained red's switch
         self._bp = self._rp = None
+        self.priority_mode, self.sample_seed, self.impl = priority, int(sample_seed), impl
+        self.priority = None
+        if priority is not None:
+            from . import replay
+            self.priority = replay.new_priority(E, cap, dev)
+            self.draw = torch.zeros(1, dtype=torch.int64, device=dev)
+            self.sample_status = torch.zeros(1, dtype=torch.int64, device=dev)
+            self._replay_buf = {}  # minibatch(), minibatch_dist(): the buffers per batch size
 
     def refresh_params(self, params=None):
         """Re-pack the networks' parameters (after a learner update). params: a
@@ -397,6 +428,9 @@ class QCollector:
         self.reward[k].copy_(out["rew_blue"] if blue_side else out["rew_red"])
         self.next_state[k].copy_(out["obs_blue"] if blue_side else out["obs_red"])
         self.done[k].copy_(out["done"])
+        if self.priority is not None:
+            from . import replay
+            replay.mark(self.priority, self.reward, k, self.priority_mode, self.impl)
         self.steps += 1
         self.t += 1
         return k
@@ -413,6 +447,63 @@ class QCollector:
         flat = lambda t: t.reshape((self.cap * E,) + tuple(t.shape[2:]))  # noqa: E731
         return dict(state=flat(self.state)[idx], action=flat(self.action)[idx], reward=flat(self.reward)[idx],
                     next_state=flat(self.next_state)[idx], done=flat(self.done)[idx], index=idx)
+
+
+    def ring(self):
+        """The ring's tensors as lnw.replay takes them."""
+        return dict(state=self.state, next_state=self.next_state, action=self.action, reward=self.reward,
+                    done=self.done)
+
+    def _replay_args(self, seed):
+        if self.priority is None:
+            raise RuntimeError("the collector keeps no priorities: QCollector(..., priority='uniform' or 'reward')")
+        return (self.filled, self.sample_seed if seed is None else int(seed), self.draw, self.sample_status,
+                self.g.env_id_base * self.cap)
+
+    def minibatch(self, batch, seed=None, advance=True):
+        """`batch` distinct transitions drawn by the priorities and packed on the
+        device (lnw_ppo_sample, then lnw_replay_pack), as the row tensors
+        QLearner.step() / grad() take: dict(state, next_state [B n, D], action
+        [B n, 4] int32, reward [B n] in the ring's dtype, done [B n] int32 (the
+        transition's, repeated per ship), key [B] float64, index [B] int64 in
+        sample()'s convention ring step * E + env, global_row [B] int64), in
+        ascending (key, global row) order. The draw is a pure function of (seed,
+        draw counter, global row): bitwise reproducible, and independent of how
+        the envs are sharded. seed: None for sample_seed. `draw` advances by one
+        unless advance is False. 1 <= batch <= min(filled * E, 131072), else
+        ValueError before anything runs: no empty slot is drawn.
+
+        A chain of launches on the current stream with no host synchronisation
+        (impl="hip"), capturable with QLearner.step in one torch.cuda.graph:
+        every replay draws afresh, the counter living on the device, and reads
+        the ring and the priorities as they are then. The row tensors are views
+        of a buffer kept per batch size that the next call of that size
+        overwrites; QLearner.rows() passes them through without a copy."""
+        from . import replay
+        filled, seed, draw, status, row_base = self._replay_args(seed)
+        return replay.minibatch(self.ring(), self.priority, batch, filled, seed, draw, status, row_base,
+                                bool(advance), self.impl, self._replay_buf)
+
+    def minibatch_dist(self, batch, seed=None, advance=True, group=None):
+        """minibatch() over the union of the ranks' collectors: every rank gets
+        the minibatch that one collector over all envs would draw with
+        minibatch(), bit for bit (the same dict without `index`, which has no
+        meaning across rings). Every rank draws `batch` candidates from its own
+        ring (batch <= its filled * E, else ValueError before any collective),
+        one all-gather exchanges the candidate lists (lnw.ppodist.message),
+        lnw_ppo_sample_merge merges them, lnw_replay_pack packs the slots this
+        rank owns, and one int32 SUM all-reduce assembles the buffer. group: the
+        process group (None: the default one; with none initialised, a world of
+        one). On "nccl" (RCCL) nothing synchronises with the host; "gloo" stages
+        through it. sample_status holds the count over all ranks.
+
+        Preconditions, not checked: every rank has the same cap, steps,
+        sample_seed (or seed) and `draw`, and the ranks' envs are disjoint ranges
+        of the global envs (env_id_base)."""
+        from . import replay
+        filled, seed, draw, status, row_base = self._replay_args(seed)
+        return replay.minibatch_dist(self.ring(), self.priority, batch, filled, seed, draw, status, row_base,
+                                     bool(advance), group, self.impl, self._replay_buf)
 
 
 # names of packed()'s segments, in its order (state_dict keys)
