@@ -15,7 +15,12 @@ __device__ __forceinline__ void adam_apply(float *p, float *m, float *v, long lo
   const float nstep = (float)(-(lr / bc1));
   const float bc2s = (float)sqrt(bc2);
   const float w1 = (float)(1.0 - beta1), w2 = (float)(1.0 - beta2), b2 = (float)beta2, epsf = (float)eps;
-  const float mi = m[i] + w1 * (gi - m[i]);
+  // exp_avg.lerp_(grad, 1 - beta1) as torch computes it on the host and on the device: one fused multiply-add
+  // onto the start point for a weight below 0.5 and onto the end point from 0.5 on (beta1 <= 0.5; at beta1 = 0
+  // that is the gradient itself). Unfused, or always from m, the rounding of w (g - m) is hundreds of ulp of a
+  // result that cancels (g against a preloaded m of the other sign).
+  const float dm = gi - m[i];
+  const float mi = w1 < 0.5f ? fmaf(w1, dm, m[i]) : fmaf(w1 - 1.0f, dm, gi);
   const float vi = v[i] * b2 + (w2 * gi) * gi;
   const float denom = sqrtf(vi) / bc2s + epsf;
   m[i] = mi;

@@ -1,15 +1,18 @@
 """Shared helpers of the MAPPO learner tests (test_ppolearn_cpu.py,
-test_gpu_ppolearn.py): the recorded sets of tests/golden/ppolearn*.npz, the
-float64 oracle, generated inputs with their preconditions, and the gradient
-check (the measure and bound of _qlearn_util)."""
+test_gpu_ppolearn.py, and through _learner_cases.py test_learner_cases_cpu.py and
+test_gpu_learner_hyper.py): the recorded sets of tests/golden/ppolearn*.npz, the
+float64 oracle, generated inputs with their preconditions, the gradient check
+(the measure and bound of _qlearn_util), a generated case and its comparison
+against the kernels, lnw_ppo_clip_adam alone, and the float64 run of K updates."""
+import ctypes as C
 import os
 
 import numpy as np
 import torch
 
 from _qlearn_util import U, bound, err  # noqa: F401
-from lnw.ppolearn import (RUNNING, actor_forward, actor_slices, critic_forward, critic_slices, flat_size, losses,
-                          popart)
+from lnw.ppolearn import (RUNNING, PPOLearner, actor_forward, actor_slices, critic_forward, critic_slices, flat_size,
+                          losses, popart)
 from lnw.rollout import BatchedActor, BatchedCritic, gae
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -218,3 +221,76 @@ def assert_rows_within(out, o64, what):
     e = err(out["advantage"], o64["advantage"])
     print(f"{what} advantage: err {e:.3e} (tolerance {TOL_ADV:.0e})")
     assert e <= TOL_ADV, (what, "advantage", e)
+
+
+def ulps(a, b):
+    a, b = a.detach().cpu().numpy(), b.detach().cpu().numpy()
+    return np.abs(a.astype(np.float64) - b) / np.spacing(np.maximum(np.abs(a), np.abs(b)).astype(np.float32))
+
+
+def close_loss(name, got, want, rel=1e-5):
+    got, want = float(got), float(want)
+    print(f"{name}: {got!r} against {want!r}")
+    assert abs(got - want) <= rel * abs(want), (name, got, want)
+
+
+def _clip_adam(theta, grad, m, v, step, clip, lr=1e-4, max_norm=1.0, betas=(0.9, 0.999), eps=1e-8):
+    from lnw import _abi
+    L = _abi.load()
+    _abi.check(L.lnw_ppo_clip_adam(theta.data_ptr(), grad.data_ptr(), m.data_ptr(), v.data_ptr(), theta.numel(),
+                                   step.data_ptr(), lr, betas[0], betas[1], eps, max_norm, clip.data_ptr(),
+                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+
+
+def generated(B, n, D, index, seed=None, sigma=2.0, hyper=None):
+    """Nets, the batch on the host, the float64 oracle and the float32 host arm's
+    result of a generated case, its preconditions asserted. hyper: the loss
+    hyperparameters off their defaults (eps_clip, entropy_coef, gamma, lambda_),
+    for the batch's margins, the host arm and the oracle alike."""
+    hyper = dict(hyper or {})
+    eps_clip = hyper.get("eps_clip", 0.2)
+    seed = 1000 * n + 7 * B + D if seed is None else seed
+    actor, critic = random_nets(n, D, seed)
+    batch = random_batch(actor, critic, B, n, D, seed + 1, index=index, sigma=sigma, eps_clip=eps_clip)
+    T = PPOLearner(actor, critic, impl="torch", device="cpu", **hyper)
+    o64 = oracle64(T.theta_actor, T.theta_critic, batch, n, D, **hyper)
+    cnt, margin_a, margin_c = branch_report(o64, batch, eps_clip)
+    print(f"B={B} n={n} D={D} {index}: {cnt} margins {margin_a:.2e} {margin_c:.2e}")
+    assert margin_a >= 1e-4 and margin_c >= 1e-4, (margin_a, margin_c)
+    if B >= 63:
+        assert min(v for k, v in cnt.items() if k.startswith("actor")) >= 8, cnt
+        assert min(v for k, v in cnt.items() if k.startswith("critic")) >= 4, cnt
+    ref = T.grad(batch, update_running=False)
+    assert_rows_within(ref, o64, "float32 host arm")
+    return actor, critic, batch, o64, ref
+
+
+def check_case(actor, critic, batch, o64, ref, what, hyper=None, **kw):
+    H = PPOLearner(actor, critic, **dict(hyper or {}), **kw)
+    out = H.grad(batch, update_running=False)
+    assert_rows_within(out, o64, what)
+    for k in ("actor_loss", "critic_loss"):
+        close_loss(f"{what} {k}", out[k], o64[k])
+    assert_grads_within(out["actor_grad"], ref["actor_grad"], o64["actor_grad"], H.actor_sl, ACTOR_GRAD_NAMES,
+                        what + " actor")
+    assert_grads_within(out["critic_grad"], ref["critic_grad"], o64["critic_grad"], H.critic_sl, CRITIC_GRAD_NAMES,
+                        what + " critic")
+    return H, out
+
+
+def steps64(actor, critic, batches, K, n, D, lr, max_grad_norm=1.0, betas=(0.9, 0.999), eps=1e-8, eps_clip=0.2,
+            entropy_coef=0.2, gamma=0.99, lambda_=0.95):
+    """K updates in float64 on the host: the oracle's gradients, clip_grad_norm_
+    and torch.optim.Adam on float64 vectors."""
+    T = PPOLearner(actor, critic, impl="torch", device="cpu")
+    pa = torch.nn.Parameter(T.theta_actor.double())
+    pc = torch.nn.Parameter(T.theta_critic.double())
+    opts = [torch.optim.Adam([p], lr=lr, betas=betas, eps=eps) for p in (pa, pc)]
+    for k in range(K):
+        o = oracle64(pa, pc, batches[k % len(batches)], n, D, eps_clip=eps_clip, entropy_coef=entropy_coef,
+                     gamma=gamma, lambda_=lambda_)
+        for p, g, opt in ((pa, o["actor_grad"], opts[0]), (pc, o["critic_grad"], opts[1])):
+            p.grad = g.clone()
+            torch.nn.utils.clip_grad_norm_([p], max_grad_norm)
+            opt.step()
+    return pa.detach(), pc.detach()

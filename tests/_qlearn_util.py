@@ -1,6 +1,8 @@
 """Shared helpers of the DDQN learner tests (test_qlearn_cpu.py,
-test_gpu_qlearn.py): the recorded sets of tests/golden/qlearn.npz, the float64
-oracle, and the error measure and bound of the gradient checks."""
+test_gpu_qlearn.py, and through _learner_cases.py test_learner_cases_cpu.py and
+test_gpu_learner_hyper.py): the recorded sets of tests/golden/qlearn.npz, the float64
+oracle, the error measure and bound of the gradient checks, generated networks
+and transition rows, and lnw_qnet_adam alone."""
 import os
 
 import numpy as np
@@ -114,3 +116,52 @@ def assert_grads_within(flat, flat_ref, o64, n_in, policy_bn, what, report=None)
         if not e[n] <= bound(er[n]):
             bad.append((n, e[n], er[n]))
     assert not bad, (what, bad)
+
+
+def check(name, got, ref, o64):
+    e, er = err(got, o64), err(ref, o64)
+    print(f"{name}: err {e:.3e} ref {er:.3e} bound {bound(er):.3e}")
+    assert e <= bound(er), (name, e, er)
+
+
+def random_net(D, seed):
+    from lnw.qlearn import BatchedQNet
+    torch.manual_seed(seed)
+    net = BatchedQNet.for_obs(D)
+    with torch.no_grad():
+        for m in (net.norm1, net.norm2):
+            m.weight.add_(0.1 * torch.randn_like(m.weight))
+            m.bias.add_(0.1 * torch.randn_like(m.bias))
+            m.running_mean.uniform_(-0.2, 0.2)
+            m.running_var.uniform_(0.5, 2.0)
+    return net
+
+
+def random_batch(B, D, seed, device="cuda"):
+    """Random transition rows. The rewards are centred at -2: the Q-values are
+    >= 0, so the residual q - y of a row is not a difference of nearly equal
+    numbers. err() is relative to the gradient's scale, and a residual that
+    cancels multiplies the float32 rounding of q and y themselves (which no
+    float32 arm avoids) by |q| / |q - y|; with two or three rows per radar
+    output that alone can pass the 8 x 2^-23 floor."""
+    g = torch.Generator().manual_seed(seed)
+
+    def obs():
+        o = torch.rand((B, D), generator=g)
+        o[:, :49] = torch.randint(0, 256, (B, 49), generator=g) / 255.0
+        return o
+
+    act = torch.stack([torch.randint(0, 2, (B,), generator=g), torch.randint(0, 5, (B,), generator=g),
+                       torch.randint(0, 50, (B,), generator=g), torch.zeros(B, dtype=torch.long)], 1)
+    return dict(state=obs().to(device), next_state=obs().to(device), action=act.to(device, torch.int32),
+                reward=(torch.randn(B, generator=g).mul(0.5) - 2.0).to(device),
+                done=(torch.rand(B, generator=g) > 0.1).to(device, torch.int32))
+
+
+def _adam(theta, grad, m, v, step, lr=1e-4, clamp=1.0, betas=(0.9, 0.999), eps=1e-8):
+    import ctypes as C
+    from lnw import _abi
+    L = _abi.load()
+    _abi.check(L.lnw_qnet_adam(theta.data_ptr(), grad.data_ptr(), m.data_ptr(), v.data_ptr(), theta.numel(),
+                               step.data_ptr(), lr, betas[0], betas[1], eps, clamp,
+                               C.c_void_p(torch.cuda.current_stream().cuda_stream)))

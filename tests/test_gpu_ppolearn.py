@@ -16,15 +16,14 @@ cannot then take another branch than the oracle), every branch populated where
 the batch is large enough to hold them, and the float32 host arm inside the
 per-row tolerances."""
 import copy
-import ctypes as C
 
 import numpy as np
 import pytest
 import torch
 
-from _ppolearn_util import (ACTOR_GRAD_NAMES, CRITIC_GRAD_NAMES, NOISE, SETS, assert_grads_within, assert_rows_within,
-                            bound, branch_report, err, gold, hyper, load_set, oracle64, random_batch, random_nets,
-                            ref_flat, segs)
+from _ppolearn_util import (ACTOR_GRAD_NAMES, CRITIC_GRAD_NAMES, NOISE, SETS, _clip_adam, assert_grads_within,
+                            assert_rows_within, branch_report, check_case, close_loss, err, generated, gold, hyper,
+                            load_set, oracle64, random_batch, random_nets, ref_flat, segs, steps64, ulps)
 from lnw.ppolearn import RUNNING, PPOLearner, running_after
 
 pytestmark = pytest.mark.gpu
@@ -33,17 +32,6 @@ pytestmark = pytest.mark.gpu
 def make(prefix, impl="hip", device="cuda", **kw):
     actor, critic, batch = load_set(prefix)
     return PPOLearner(actor, critic, impl=impl, device=device, **hyper(prefix), **kw), batch
-
-
-def ulps(a, b):
-    a, b = a.detach().cpu().numpy(), b.detach().cpu().numpy()
-    return np.abs(a.astype(np.float64) - b) / np.spacing(np.maximum(np.abs(a), np.abs(b)).astype(np.float32))
-
-
-def close_loss(name, got, want, rel=1e-5):
-    got, want = float(got), float(want)
-    print(f"{name}: {got!r} against {want!r}")
-    assert abs(got - want) <= rel * abs(want), (name, got, want)
 
 
 @pytest.mark.parametrize("prefix", SETS)
@@ -84,14 +72,6 @@ def test_grad_matches_reference_and_float64(prefix):
         keep[k:k + shp[0]] = False
     assert torch.equal(L.theta_actor[keep], tha0[keep]) and torch.equal(L.theta_critic, thc0)
     assert int(L.nbt) == int(g[f"{prefix}.actor.before.norm1.num_batches_tracked"]) + 64
-
-
-def _clip_adam(theta, grad, m, v, step, clip, lr=1e-4, max_norm=1.0):
-    from lnw import _abi
-    L = _abi.load()
-    _abi.check(L.lnw_ppo_clip_adam(theta.data_ptr(), grad.data_ptr(), m.data_ptr(), v.data_ptr(), theta.numel(),
-                                   step.data_ptr(), lr, 0.9, 0.999, 1e-8, max_norm, clip.data_ptr(),
-                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)))
 
 
 @pytest.mark.parametrize("which", ["actor", "critic"])
@@ -148,38 +128,6 @@ def test_clip_adam_against_torch():
         d = (theta - p.detach()).abs().cpu().numpy()
         tol = 2 * np.spacing(np.abs(p.detach().cpu().numpy())) + 1e-3 * 2.0 ** -21
         assert (d <= tol).all(), (k, d.max())
-
-
-def generated(B, n, D, index, seed=None, sigma=2.0):
-    """Nets, the batch on the host, the float64 oracle and the float32 host arm's
-    result of a generated case, its preconditions asserted."""
-    seed = 1000 * n + 7 * B + D if seed is None else seed
-    actor, critic = random_nets(n, D, seed)
-    batch = random_batch(actor, critic, B, n, D, seed + 1, index=index, sigma=sigma)
-    T = PPOLearner(actor, critic, impl="torch", device="cpu")
-    o64 = oracle64(T.theta_actor, T.theta_critic, batch, n, D)
-    cnt, margin_a, margin_c = branch_report(o64, batch, 0.2)
-    print(f"B={B} n={n} D={D} {index}: {cnt} margins {margin_a:.2e} {margin_c:.2e}")
-    assert margin_a >= 1e-4 and margin_c >= 1e-4, (margin_a, margin_c)
-    if B >= 63:
-        assert min(v for k, v in cnt.items() if k.startswith("actor")) >= 8, cnt
-        assert min(v for k, v in cnt.items() if k.startswith("critic")) >= 4, cnt
-    ref = T.grad(batch, update_running=False)
-    assert_rows_within(ref, o64, "float32 host arm")
-    return actor, critic, batch, o64, ref
-
-
-def check_case(actor, critic, batch, o64, ref, what, **kw):
-    H = PPOLearner(actor, critic, **kw)
-    out = H.grad(batch, update_running=False)
-    assert_rows_within(out, o64, what)
-    for k in ("actor_loss", "critic_loss"):
-        close_loss(f"{what} {k}", out[k], o64[k])
-    assert_grads_within(out["actor_grad"], ref["actor_grad"], o64["actor_grad"], H.actor_sl, ACTOR_GRAD_NAMES,
-                        what + " actor")
-    assert_grads_within(out["critic_grad"], ref["critic_grad"], o64["critic_grad"], H.critic_sl, CRITIC_GRAD_NAMES,
-                        what + " critic")
-    return H, out
 
 
 SHAPE_CASES = [(B, 4, 68, "shuffled") for B in (2, 63, 64, 65, 129, 257, 4096)]
@@ -387,22 +335,6 @@ def test_step_clip_against_torch_arm(max_norm):
             solid = g[nm].abs() > 1e-6
             d = (a[nm] - b[nm]).abs()
             assert float(d[solid].max() if solid.any() else 0.0) <= 0.02 * H.lr, (nm, float(d.max()))
-
-
-def steps64(actor, critic, batches, K, n, D, lr):
-    """K updates in float64 on the host: the oracle's gradients, clip_grad_norm_
-    and torch.optim.Adam on float64 vectors."""
-    T = PPOLearner(actor, critic, impl="torch", device="cpu")
-    pa = torch.nn.Parameter(T.theta_actor.double())
-    pc = torch.nn.Parameter(T.theta_critic.double())
-    opts = [torch.optim.Adam([p], lr=lr) for p in (pa, pc)]
-    for k in range(K):
-        o = oracle64(pa, pc, batches[k % len(batches)], n, D)
-        for p, g, opt in ((pa, o["actor_grad"], opts[0]), (pc, o["critic_grad"], opts[1])):
-            p.grad = g.clone()
-            torch.nn.utils.clip_grad_norm_([p], 1.0)
-            opt.step()
-    return pa.detach(), pc.detach()
 
 
 def test_twenty_steps_against_torch_arm():

@@ -13,8 +13,8 @@ import numpy as np
 import pytest
 import torch
 
-from _qlearn_util import (GRAD_NAMES, NOISE, RUNNING, SETS, assert_grads_within, bound, err, gold, load_set, oracle64,
-                          ref_grad_flat, segs)
+from _qlearn_util import (GRAD_NAMES, NOISE, RUNNING, SETS, _adam, assert_grads_within, bound, check, err, gold,
+                          load_set, oracle64, random_batch, random_net, ref_grad_flat, segs)
 
 pytestmark = pytest.mark.gpu
 
@@ -26,46 +26,6 @@ def make(prefix, policy_bn, impl="hip", device="cuda", **kw):
     kw.setdefault("lr", float(g[f"{prefix}_lr"]))
     return QLearner(pol, tgt, gamma=float(g[f"{prefix}_gamma"]), policy_bn=policy_bn, impl=impl, device=device,
                     **kw), batch
-
-
-def check(name, got, ref, o64):
-    e, er = err(got, o64), err(ref, o64)
-    print(f"{name}: err {e:.3e} ref {er:.3e} bound {bound(er):.3e}")
-    assert e <= bound(er), (name, e, er)
-
-
-def random_net(D, seed):
-    from lnw.qlearn import BatchedQNet
-    torch.manual_seed(seed)
-    net = BatchedQNet.for_obs(D)
-    with torch.no_grad():
-        for m in (net.norm1, net.norm2):
-            m.weight.add_(0.1 * torch.randn_like(m.weight))
-            m.bias.add_(0.1 * torch.randn_like(m.bias))
-            m.running_mean.uniform_(-0.2, 0.2)
-            m.running_var.uniform_(0.5, 2.0)
-    return net
-
-
-def random_batch(B, D, seed, device="cuda"):
-    """Random transition rows. The rewards are centred at -2: the Q-values are
-    >= 0, so the residual q - y of a row is not a difference of nearly equal
-    numbers. err() is relative to the gradient's scale, and a residual that
-    cancels multiplies the float32 rounding of q and y themselves (which no
-    float32 arm avoids) by |q| / |q - y|; with two or three rows per radar
-    output that alone can pass the 8 x 2^-23 floor."""
-    g = torch.Generator().manual_seed(seed)
-
-    def obs():
-        o = torch.rand((B, D), generator=g)
-        o[:, :49] = torch.randint(0, 256, (B, 49), generator=g) / 255.0
-        return o
-
-    act = torch.stack([torch.randint(0, 2, (B,), generator=g), torch.randint(0, 5, (B,), generator=g),
-                       torch.randint(0, 50, (B,), generator=g), torch.zeros(B, dtype=torch.long)], 1)
-    return dict(state=obs().to(device), next_state=obs().to(device), action=act.to(device, torch.int32),
-                reward=(torch.randn(B, generator=g).mul(0.5) - 2.0).to(device),
-                done=(torch.rand(B, generator=g) > 0.1).to(device, torch.int32))
 
 
 @pytest.mark.parametrize("prefix,policy_bn", SETS)
@@ -118,15 +78,6 @@ def test_freeze_running_leaves_both_vectors():
     assert torch.equal(L.theta, theta0) and torch.equal(L.theta_target, target0) and L.nbt.tolist() == [0, 0]
     b = L.grad(batch, update_running=False)
     assert torch.equal(a["grad"], b["grad"]) and torch.equal(a["loss"], b["loss"])
-
-
-def _adam(theta, grad, m, v, step, lr=1e-4, clamp=1.0):
-    import ctypes as C
-    from lnw import _abi
-    L = _abi.load()
-    _abi.check(L.lnw_qnet_adam(theta.data_ptr(), grad.data_ptr(), m.data_ptr(), v.data_ptr(), theta.numel(),
-                               step.data_ptr(), lr, 0.9, 0.999, 1e-8, clamp,
-                               C.c_void_p(torch.cuda.current_stream().cuda_stream)))
 
 
 def ulps(a, b):
