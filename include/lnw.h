@@ -421,6 +421,19 @@ typedef struct lnw_policy_args {
                                   obs_env_stride == this stride: the rows already sit in the rollout
                                   buffer (lnw_observe_ex wrote them there), and only the rows of
                                   envs whose episode ended (live == 0) are zeroed in place */
+  int32_t script_self;         /* != 0: this launch's own rows are scripted (the reference's warm-up
+                                  of a learning red side, ppo.py:552-557). Ship i takes the row
+                                  script[(i * script_steps + t) * 4 ..]; a row past the table (i >=
+                                  script_n or t >= script_steps) is zeros. full gets the float64 row
+                                  as it stands in the table (zeros for a sunk ship), act_out the row
+                                  rounded to float32 and logp_out its log-probability under params
+                                  (get_dist, as forced: no NaN guard), both zeros for rows not kept
+                                  (!alive or !live). No keyed draw is consumed and T is not read.
+                                  Needs script (32-B aligned); LNW_EINVAL together with forced.
+                                  script_own0 / script_cnt keep their meaning (the other side's rows,
+                                  written by the lane of ship 0) and may be used in the same launch;
+                                  obs_out, kinds, f32_out, live and alive behave as without it.
+                                  Appended last: zero-initialised callers see no change */
 } lnw_policy_args;
 int lnw_policy_act(const lnw_policy_args *args, void *stream);
 
@@ -460,7 +473,9 @@ int lnw_policy_act(const lnw_policy_args *args, void *stream);
  *     (slot << 40) + 2 P m + k and + P + k, through Box-Muller.
  *   slot = (call * T) * 4 + 3, call read from call_dev (NULL = 0): a rollout's
  *     action draws use slots (call * T + t) * 4 + which with which 0 (blue
- *     sample), 1 (blue action noise) and 2 (red sample) only, so which = 3 of
+ *     sample), 1 (blue action noise) and 2 (red sample), and which = 3 only for
+ *     the action noise of a learning red actor (noise > 0 at which = 2), which
+ *     lnw.rollout.Rollout refuses at step 0 beside parameter noise: which = 3 of
  *     step 0 is free. (member0 + members) * 2 P must stay below 2^40.
  *   sigma = noise_dev[0], clip = noise_dev[1], read on the device, so a captured
  *     graph follows in-place updates of the schedule. noise_dev == NULL or sigma

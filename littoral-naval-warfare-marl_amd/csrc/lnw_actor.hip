@@ -113,7 +113,9 @@ __global__ __launch_bounds__(CH_THREADS, 1) void features_kernel(const float *pa
 //   NaN heads -> N(0, 1) for the row (the reference returns None there);
 //   sample: N(mean, std) from keyed Philox normals (+ N(0, noise)), clamped to
 //   [0, 1], and its log-probability; or, forced, the log-probability of given
-//   actions (get_dist);
+//   actions (get_dist); or, script_self, that of the side's own scripted row
+//   (a learning red side's warm-up, ppo.py:552-557), the row's float64 value
+//   going to lnw_step as it stands in the table, no draw consumed;
 //   outputs: the f64 action rows of lnw_step (sunk ships 0), the rollout's
 //   action / log-probability rows (0 after the episode ended) and the
 //   observation copy for the rollout buffer; the lane of ship 0 also writes its
@@ -555,6 +557,17 @@ __global__ __launch_bounds__(PA_THREADS, 1) void policy_act_kernel(PolicyKernelA
     const float *fa = a.forced_act + (long long)e_o * a.fa_env_stride + 4 * i_o;
 #pragma unroll
     for (int o = 0; o < NOUT; o++) act[o] = fa[o];
+  } else if (a.script_self) {  // the side's own scripted rows (ppo.py:552-557): get_dist of the f32 row
+    f64x4 sv = {0.0, 0.0, 0.0, 0.0};
+    if (i_o < a.script_n && a.t < a.script_steps)
+      sv = *(const f64x4 *)(a.script + ((long long)i_o * a.script_steps + a.t) * 4);
+#pragma unroll
+    for (int o = 0; o < NOUT; o++) act[o] = (float)sv[o];
+    // the step takes the table's float64 row itself, not the rounded one
+    if (a.full) {
+      if (!alive) sv = f64x4{0.0, 0.0, 0.0, 0.0};
+      *(f64x4 *)(a.full + ((long long)e_o * a.A + a.own0 + i_o) * 4) = sv;
+    }
   } else {
     if (!ok) {
 #pragma unroll
@@ -585,13 +598,13 @@ __global__ __launch_bounds__(PA_THREADS, 1) void policy_act_kernel(PolicyKernelA
     // where an f32 exp overflows to inf or rounds to 0 (below ln 2^-150; the hardware
     // exp may flush the denormals above that, whose log the log-scale stays), as
     // torch's log(exp(.)) does; v_rcp_f32 for 1 / var (1 ulp)
-    const float l = (a.forced || ok) ? lsd[o] : 0.f;
+    const float l = (a.forced || a.script_self || ok) ? lsd[o] : 0.f;
     const float ls = (s < INFINITY && l > -103.972f) ? l : logf(s);
     lp[o] = -(d * d) * (0.5f * __builtin_amdgcn_rcpf(s * s)) - ls - 0.91893853320467274178f;
   }
   // ---- outputs --------------------------------------------------------------
   const bool keep = alive && live;
-  if (a.full) {
+  if (a.full && !a.script_self) {
     f64x4 v = {alive ? (double)act[0] : 0.0, alive ? (double)act[1] : 0.0, alive ? (double)act[2] : 0.0,
                alive ? (double)act[3] : 0.0};
     *(f64x4 *)(a.full + ((long long)e_o * a.A + a.own0 + i_o) * 4) = v;
@@ -793,7 +806,8 @@ static int policy_launch(const lnw_policy_args *args, const lnw_policy_pop *pop,
     return LNW_EINVAL;
   if (!obs_width_ok(a.D, true)) return LNW_EUNSUPPORTED;
   if (a.forced && !a.forced_act) return LNW_EINVAL;
-  if (!a.forced && a.T <= 0) return LNW_EINVAL;
+  if (a.script_self && (!a.script || a.forced)) return LNW_EINVAL;
+  if (!a.forced && !a.script_self && a.T <= 0) return LNW_EINVAL;
   if (a.script && (!a.full || a.script_own0 < 0 || a.script_own0 + a.script_cnt > a.A)) return LNW_EINVAL;
   if ((a.kinds_f32_all_alive || a.f32_out) && !a.kinds) return LNW_EINVAL;
   if (a.obs_in_env_stride < 0 || (a.obs_in_env_stride && (a.obs_in_env_stride < (int64_t)a.n * a.D ||

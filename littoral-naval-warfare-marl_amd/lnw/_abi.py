@@ -90,7 +90,7 @@ class PolicyArgs(C.Structure):  # include/lnw.h: lnw_policy_args
                 ("script_n", C.c_int32), ("script_steps", C.c_int32), ("script_own0", C.c_int32),
                 ("script_cnt", C.c_int32), ("kinds", C.c_void_p), ("kinds_f32_all_alive", C.c_int32),
                 ("f32_out", C.c_void_p), ("f32_env_stride", C.c_int64),
-                ("obs_in_env_stride", C.c_int64)]
+                ("obs_in_env_stride", C.c_int64), ("script_self", C.c_int32)]
 
 
 class ActorPerturbArgs(C.Structure):  # include/lnw.h: lnw_actor_perturb_args

@@ -1,5 +1,7 @@
 """The learner half of the MAPPO loop: one minibatch update of the reference's
-PPO.learn (ppo.py:321-390) for the blue side, on flat device vectors.
+PPO.learn (ppo.py:321-390) for one side, on flat device vectors: the side whose
+actor and critic it is given (n ships and rows of D floats follow from their
+shapes), blue, or red from a Rollout(side="red").
 
 Reference: ppo.py:673-693 (evaluate), ppo.py:695-714 (gae, over the minibatch
 rows as the sequence), ppo.py:716-729 (popart_normalize), ppo.py:342-362 (the
@@ -9,8 +11,7 @@ ppo.py:311-319 (the prioritised sampler). The kernels are csrc/lnw_ppolearn.hip
 the keyed minibatch draw behind PPOLearner.minibatch) and csrc/lnw_ppodist.hip
 (the merge and the row exchange behind PPOLearner.minibatch_dist, which trains
 on rollouts sharded over ranks: lnw/ppodist.py). learn()'s outer schedule
-(noise ratio, lr halving on victories, epoch count) and red-side training stay
-with the caller;
+(noise ratio, lr halving on victories, epoch count) stays with the caller;
 parameter noise is the rollout's (lnw.rollout.Rollout(param_noise=..., theta=
 learner.theta_actor) acts from this learner's flat vector).
 """
@@ -205,7 +206,8 @@ def sample_keys(rtg, seed, slot, row_base=0):
 
 
 class PPOLearner:
-    """PPO.learn's minibatch update (ppo.py:321-390) for the blue side on flat
+    """PPO.learn's minibatch update (ppo.py:321-390) for one side (blue, or red
+    given the red actor and critic and a Rollout(side="red")'s buffers) on flat
     device vectors: `theta_actor` (actor_slices layout) and `theta_critic`
     (critic_slices layout), each with Adam moments `m`, `v` and a device step
     counter.

@@ -323,7 +323,9 @@ def perturbed_theta(theta, member0, members, std, clip, seed, call, T, dtype=tor
     theta_m = theta + mask * clamp(std * z_m, -clip, +clip) (ppo.py:474-475) with
     z_m = keyed_normal(row0 = m, rows = 1, cols = P, seed, slot = call * T * 4 + 3):
     slot 3 of the rollout's first step, which no action draw uses (0: blue
-    sample, 1: blue action noise, 2: red sample). std == 0 returns theta itself.
+    sample, 1: blue action noise, 2: red sample; 3 is a learning red actor's
+    action noise, which Rollout refuses at step 0 beside parameter noise).
+    std == 0 returns theta itself.
     dtype=torch.float64 evaluates the same uniforms in double (tests)."""
     theta = theta.reshape(-1)
     P = theta.numel()
@@ -408,8 +410,9 @@ STRIDED_POLICY_INPUT = True
 
 
 class Rollout:
-    """Batched MAPPO rollout (ppo.py:421-671, side being trained = blue): env e
-    plays one rollout episode; all E envs advance together. Every step t:
+    """Batched MAPPO rollout (ppo.py:421-671; the side being trained is blue,
+    or red with side="red", below): env e plays one rollout episode; all E envs
+    advance together. Every step t (told for side="blue"):
 
       1. observe (ppo.py:497-575): `ship.get_obs()` of every live ship, blue
          then red, with its side effects (target lists, EW gauss draws) — one
@@ -489,16 +492,78 @@ class Rollout:
     too) and every blue policy launch through lnw_policy_act_pop; the returned
     buffers hold "member" [E] int64, the global member of each env. With none
     of these arguments the rollout issues exactly the launches it did.
+
+    Red-side training (ppo.py's rollout with SIDE == "red"): `side="red"` on a
+    game whose scenario plays red (game.sc.side: the step's rewards and
+    engagement rules follow it) collects the red side instead. `red_actor` is
+    the learning actor, `actor` the frozen blue one (both required; red="script"
+    is refused), `critic` the red critic BatchedCritic(Dr * nr). The buffers are
+    the red rows' ([E, T, nr, Dr], [E, T, nr, 4], rewards from rew_red,
+    reference_rtg over nr); `param_noise`, `envs_per_member`, `theta` and
+    `member_thetas` apply to the red actor (the flat layout for Dr). Blue acts
+    with running BatchNorm statistics and stores nothing (ppo.py:519-526).
+      * `warmup` (default 15, the reference's `s > 14`; 0 <= warmup <= steps; only
+        with side="red"): for t < warmup red takes its scripted profiles
+        (ppo.py:552-557; lnw_policy_act's script_self) and the step's rows are
+        float64; from t >= warmup red is sampled from the red actor, and the
+        rows are float32 when every ship is alive. The returned buffers hold
+        "sampled" [E, T] bool, True where the rows came from the actor (t >=
+        warmup and the episode running): a caller can leave the scripted rows
+        out of a minibatch with it.
+      * `bn` / `red_bn` None (the default) resolve to "sample" for the learning
+        side's actor and "running" for the other's; explicit strings keep their
+        meaning by colour.
+      * keyed draws: the blue sample is slot `which` 0 (rows env_id_base * nb),
+        the red sample 2 (rows env_id_base * nr), the learning red actor's
+        action noise 3. lnw_actor_perturb uses slot 3 of step 0, so side="red"
+        with `noise`, `param_noise` and warmup == 0 together is refused.
+      * `forced_actions` [E, T, A, 4] replays both sides; in the warm-up the red
+        rows come from the profiles.
+    Differences from the reference's red-side loop, by design, all in the
+    warm-up: the observation rows and the scripted actions are stored (the
+    reference stores zeros); the log-probabilities are the red actor's (the
+    reference stores the blue actor's get_dist of the red rows); the value is
+    taken on the real rows (the reference's critic sees zeros). A red ship sunk
+    after the warm-up stores zero rows, as a sunk blue ship does (the reference
+    raises there, ppo.py:547). Pinned to recordings of the reference's loop
+    (tests/golden/make_redside_golden.py), which runs only 3v3 and only while
+    no red ship is lost after step 14.
     """
 
-    def __init__(self, game: BatchedGame, actor, critic=None, steps=40, red="script",
-                 red_actor=None, noise=None, bn="sample", red_bn="running", gamma=0.99,
+    def __init__(self, game: BatchedGame, actor=None, critic=None, steps=40, red=None,
+                 red_actor=None, noise=None, bn=None, red_bn=None, gamma=0.99,
                  stop_at_done=True, observe="fresh", keyed_seed=None, impl="hip", seed=0,
-                 param_noise=None, envs_per_member=None, theta=None, member_thetas=None):
+                 param_noise=None, envs_per_member=None, theta=None, member_thetas=None,
+                 side="blue", warmup=None):
         if observe not in ("fresh", "step"):
             raise ValueError("observe must be 'fresh' or 'step'")
         if impl not in ("hip", "torch"):
             raise ValueError("impl must be 'hip' or 'torch'")
+        if side not in ("blue", "red"):
+            raise ValueError("side must be 'blue' or 'red'")
+        if red is None:  # blue trains against the scripted profiles, red against the blue actor
+            red = "script" if side == "blue" else "actor"
+        if side == "blue":
+            if warmup is not None:
+                raise ValueError("warmup needs side='red'")
+            warmup = 0
+        else:
+            if game.sc.side != side:
+                raise ValueError(f"the game's scenario plays side {game.sc.side!r}: the step's rewards and "
+                                 "engagement rules follow it, so Rollout(side='red') needs Scenario(side='red')")
+            if red == "script":
+                raise ValueError("side='red' trains the red actor: red='script' is refused")
+            if red_actor is None:
+                raise ValueError("side='red' needs red_actor, the learning actor")
+            if actor is None:
+                raise ValueError("side='red' needs actor, the frozen blue actor")
+            if warmup is None:
+                warmup = min(15, int(steps))  # the reference's `s > 14` (ppo.py:552)
+            if int(warmup) != warmup or not 0 <= warmup <= int(steps):
+                raise ValueError("warmup must be an integer in [0, steps]")
+            if noise is not None and param_noise is not None and warmup == 0:
+                raise ValueError("side='red' with noise, param_noise and warmup == 0: the action noise of "
+                                 "step 0 and lnw_actor_perturb would share keyed slot 3")
         if envs_per_member is None:
             if param_noise is not None or member_thetas is not None:
                 raise ValueError("envs_per_member is required with param_noise or member_thetas")
@@ -526,13 +591,18 @@ class Rollout:
         self.keyed_seed, self.impl, self.seed = keyed_seed, impl, int(seed)
         self.g, self.actor, self.critic = game, actor, critic
         self.T, self.red, self.red_actor = int(steps), red, red_actor
-        self.noise, self.bn, self.red_bn = noise, bn, red_bn
+        self.side, self.warmup = side, int(warmup)
+        # BatchNorm modes: by default the learning side's actor runs in training
+        # mode on batch-1 calls (per-row statistics), the other side's in eval mode
+        self.bn = bn if bn is not None else ("sample" if side == "blue" else "running")
+        self.red_bn = red_bn if red_bn is not None else ("running" if side == "blue" else "sample")
+        self.noise = noise
         self.gamma, self.stop_at_done, self.observe = float(gamma), stop_at_done, observe
-        self.table = red_script_table(game.device) if red == "script" else None
+        self.table = red_script_table(game.device) if red == "script" or self.warmup > 0 else None
         # diagnostics / parity: keep each step's action array and row kinds as
         # the policy wrote them (before the step's in-place salvo write-back)
         # in the returned buffers ("step_actions" [E, T, A, 4] float64,
-        # "step_kinds" [E, T, A]); hip impl only
+        # "step_kinds" [E, T, A])
         self.record_actions = False
         # rollout index of the keyed draws, on the device (advanced by run())
         self._call = torch.zeros(1, dtype=torch.int64, device=game.device)
@@ -543,6 +613,14 @@ class Rollout:
         if value is not None:
             self._call.fill_(int(value))
         return int(self._call.item())
+
+    def _learning(self):
+        """The side being trained: (its actor, ships n, row length D, first agent
+        slot, keyed-draw slot `which` of its sample, its BatchNorm mode)."""
+        g = self.g
+        if self.side == "red":
+            return self.red_actor, g.nr, g.Dr, g.nb, 2, self.red_bn
+        return self.actor, g.nb, g.Db, 0, 0, self.bn
 
     @torch.no_grad()
     def run(self, generator=None, forced_actions=None, on_step=None):
@@ -563,7 +641,8 @@ class Rollout:
         flag (masked ones as zeros) — so the 1.4 GB observation buffer of a
         32 768-env rollout is not zero-filled first (≈7 µs per step)."""
         g = self.g
-        E, nb, A, D, T, dev = g.E, g.nb, g.A, g.Db, self.T, g.device
+        _, nb, D, _, _, _ = self._learning()  # (the learning side's ships and row length)
+        E, T, dev = g.E, self.T, g.device
         z = torch.zeros if fill else torch.empty
         return dict(obs=z((E, T, nb, D), dtype=torch.float32, device=dev),
                     actions=z((E, T, nb, 4), dtype=torch.float32, device=dev),
@@ -579,7 +658,8 @@ class Rollout:
         the module's parameters packed into the flat layout."""
         from .ppolearn import pack
         dev = self.g.device
-        sl, P = _flat_layout(self.actor.layernorm.normalized_shape[0])
+        actor = self._learning()[0]
+        sl, P = _flat_layout(actor.layernorm.normalized_shape[0])
         if self.member_thetas is not None:
             src = self.member_thetas.to(device=dev, dtype=torch.float32).contiguous()
         elif self.theta is not None:
@@ -587,14 +667,14 @@ class Rollout:
             if src.dtype != torch.float32 or src.device != dev or not src.is_contiguous() or src.dim() != 1:
                 raise ValueError("theta must be a contiguous float32 vector on the game's device")
         else:
-            src = pack(self.actor, sl).to(dev)
+            src = pack(actor, sl).to(dev)
         if src.shape[-1] != P:
             raise ValueError(f"the flat actor vector holds {P} floats, not {src.shape[-1]}")
         return src
 
     def _member_actors(self, seed):
         """torch impl: None, or (G, the members' actors as modules) — scratch
-        copies of the blue actor loaded from the members' flat vectors."""
+        copies of the learning side's actor loaded from the members' flat vectors."""
         import copy
         if self.G is None and self.theta is None:
             return None
@@ -605,10 +685,11 @@ class Rollout:
         if src.dim() == 1:
             std, clip = self.param_noise.tolist() if self.param_noise is not None else (0.0, 0.0)
             src = perturbed_theta(src, g.env_id_base // G, M, std, clip, seed, int(self._call.item()), self.T)
-        sl, _ = _flat_layout(self.actor.layernorm.normalized_shape[0])
+        actor = self._learning()[0]
+        sl, _ = _flat_layout(actor.layernorm.normalized_shape[0])
         actors = []
         for k in range(M):
-            net = copy.deepcopy(self.actor)
+            net = copy.deepcopy(actor)
             sd = net.state_dict()  # (tensors sharing the copy's storage)
             for name, (o, shp) in sl.items():
                 sd[name].copy_(src[k, o:o + int(np.prod(shp))].reshape(shp))
@@ -623,13 +704,18 @@ class Rollout:
         g = self.g
         E, nb, nr, A, Db, Dr, T = g.E, g.nb, g.nr, g.A, g.Db, g.Dr, self.T
         dev = g.device
+        red_side = self.side == "red"
+        # the learning side: its rows fill the buffers, its launch writes the kinds
+        lactor, n, D, own0, which, lbn = self._learning()
         b = self._buffers(fill=False)
         obs, acts, logp, rew, val, running, f32s = (b[k] for k in ("obs", "actions", "log_probs", "rewards",
                                                                 "values", "running", "f32_step"))
         full = torch.zeros((E, A, 4), dtype=torch.float64, device=dev)
         kinds = torch.full((E, A), _abi.LNW_KIND_F64, dtype=torch.uint8, device=dev)
         live = torch.ones(E, dtype=torch.bool, device=dev)
-        red_actor_rows = self.red != "script" and self.red_actor is not None
+        # the other side's rows from an actor: a blue rollout's red actor, a red
+        # rollout's frozen blue actor (its launch writes action rows only)
+        other_rows = red_side or (self.red != "script" and self.red_actor is not None)
         seed = int(self.keyed_seed if self.keyed_seed is not None else self.seed) & (2**64 - 1)
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         pop = None
@@ -637,13 +723,13 @@ class Rollout:
             # the members' packed sets [M, floats] from the flat vector(s), on the device
             src = self._flat_source()
             M = -(-E // self.G) if self.G else 1
-            floats = int(L.lnw_policy_packed_floats(Db))
+            floats = int(L.lnw_policy_packed_floats(D))
             if floats <= 0:
-                raise _abi.LnwError(f"the policy kernel does not support rows of {Db} floats")
+                raise _abi.LnwError(f"the policy kernel does not support rows of {D} floats")
             ap = torch.empty((M, floats), dtype=torch.float32, device=dev)
             pt = _abi.ActorPerturbArgs()
             pt.theta, pt.theta_member_stride = src.data_ptr(), (src.shape[1] if src.dim() == 2 else 0)
-            pt.D, pt.T = Db, T
+            pt.D, pt.T = D, T
             pt.member0, pt.members = (g.env_id_base // self.G if self.G else 0), M
             pt.packed_out, pt.member_stride = ap.data_ptr(), floats
             pt.noise_dev = self.param_noise.data_ptr() if self.param_noise is not None else None
@@ -653,11 +739,16 @@ class Rollout:
                 pop = _abi.PolicyPop(self.G, floats)
                 b["member"] = torch.arange(E, dtype=torch.int64, device=dev) // self.G + pt.member0
         else:
-            ap = self.actor.packed_policy()
-        cp = self.critic.packed(nb, Db) if self.critic is not None else None
+            ap = lactor.packed_policy()
+        cp = self.critic.packed(n, D) if self.critic is not None else None
         if cp is None:  # (no critic: nothing writes the values, which are zeros)
             val.zero_()
-        rap = self.red_actor.packed_policy() if red_actor_rows else None
+        if red_side:
+            oactor, on, oD, oown0, owhich, obn, obuf, lbuf = self.actor, nb, Db, 0, 0, self.bn, g.obs_blue, g.obs_red
+        else:
+            oactor, on, oD, oown0, owhich, obn, obuf, lbuf = (self.red_actor, nr, Dr, nb, 2, self.red_bn,
+                                                             g.obs_red, g.obs_blue)
+        oap = oactor.packed_policy() if other_rows else None
         fa = None
         if forced_actions is not None:
             fa = forced_actions.to(device=dev, dtype=torch.float32).contiguous()
@@ -669,68 +760,76 @@ class Rollout:
         P = lambda t_: t_.data_ptr()  # noqa: E731
         f4, f8 = 4, 8
         table = self.table.contiguous() if self.table is not None else None
-        rew_f64 = int(g.rew_blue.dtype == torch.float64)
-        # fresh observations with no per-step callback: the blue rows go straight
-        # into the rollout buffer (lnw_observe_ex; the policy zeroes ended envs'
-        # rows in place), red's only where a red actor reads them, and the step
-        # writes none (ppo.py:577 discards them). g.obs_blue is not updated then.
+        rew_side = g.rew_red if red_side else g.rew_blue
+        rew_f64 = int(rew_side.dtype == torch.float64)
+        # fresh observations with no per-step callback: the learning side's rows go
+        # straight into the rollout buffer (lnw_observe_ex; the policy zeroes ended
+        # envs' rows in place), the other side's only where an actor reads them,
+        # and the step writes none (ppo.py:577 discards them). The game's packed
+        # buffer of the learning side (g.obs_blue, or g.obs_red) is not updated then.
         direct = self.observe == "fresh" and on_step is None
         # (STRIDED_POLICY_INPUT: the policy reads the rows in the buffer itself)
         strided = direct and STRIDED_POLICY_INPUT
         if self.observe == "step":
             g.observe(-1)
         for t in range(T):
-            row_t = P(obs) + t * nb * Db * f4  # the rollout buffer's rows of step t
-            red_rows = P(g.obs_red) if red_actor_rows else None
-            if strided:
-                g.observe_into(-1, row_t, T * nb * Db, red_rows, 0)
-            elif direct:
-                g.observe_into(-1, P(g.obs_blue), 0, red_rows, 0)
+            row_t = P(obs) + t * n * D * f4  # the rollout buffer's rows of step t
+            if direct:
+                lrows, lstride = (row_t, T * n * D) if strided else (P(lbuf), 0)
+                orows = P(obuf) if other_rows else None
+                if red_side:
+                    g.observe_into(-1, orows, 0, lrows, lstride)
+                else:
+                    g.observe_into(-1, lrows, lstride, orows, 0)
             elif self.observe == "fresh":
                 g.observe(-1)
+            scripted = t < self.warmup  # the learning side's warm-up (side red): its own rows scripted
             pa = PolicyArgs()
-            pa.obs, pa.E, pa.n, pa.D, pa.own0, pa.A = (row_t if strided else P(g.obs_blue)), E, nb, Db, 0, A
-            pa.obs_in_env_stride = T * nb * Db if strided else 0
-            pa.params, pa.bn_running = P(ap), int(self.bn == "running")
-            if fa is not None:
-                pa.forced, pa.forced_act, pa.fa_env_stride = 1, P(fa) + t * A * 4 * f4, T * A * 4
+            pa.obs, pa.E, pa.n, pa.D, pa.own0, pa.A = (row_t if strided else P(lbuf)), E, n, D, own0, A
+            pa.obs_in_env_stride = T * n * D if strided else 0
+            pa.params, pa.bn_running = P(ap), int(lbn == "running")
+            if scripted:
+                pa.script_self = 1
+                pa.script, pa.script_n, pa.script_steps = P(table), table.shape[0], table.shape[1]
+            elif fa is not None:
+                pa.forced, pa.forced_act, pa.fa_env_stride = 1, P(fa) + (t * A + own0) * 4 * f4, T * A * 4
             pa.noise = float(self.noise) if self.noise is not None else 0.0
-            pa.seed, pa.call_dev, pa.T, pa.t, pa.which = seed, P(self._call), T, t, 0
-            pa.row_base = g.env_id_base * nb
+            pa.seed, pa.call_dev, pa.T, pa.t, pa.which = seed, P(self._call), T, t, which
+            pa.row_base = g.env_id_base * n
             pa.alive = alive_p
             pa.live = P(live) if self.stop_at_done else None
-            pa.obs_out, pa.obs_env_stride = row_t, T * nb * Db
-            pa.act_out, pa.logp_out = P(acts) + t * nb * 4 * f4, P(logp) + t * nb * 4 * f4
-            pa.act_env_stride = T * nb * 4
+            pa.obs_out, pa.obs_env_stride = row_t, T * n * D
+            pa.act_out, pa.logp_out = P(acts) + t * n * 4 * f4, P(logp) + t * n * 4 * f4
+            pa.act_env_stride = T * n * 4
             pa.full = P(full)
-            if table is not None:
+            if self.red == "script":  # (side blue) the lane of ship 0 writes red's scripted rows
                 pa.script, pa.script_n, pa.script_steps = P(table), table.shape[0], table.shape[1]
                 pa.script_own0, pa.script_cnt = nb, nr
-            pa.kinds, pa.kinds_f32_all_alive = P(kinds), int(red_actor_rows)
+            pa.kinds, pa.kinds_f32_all_alive = P(kinds), int(other_rows and not scripted)
             pa.f32_out, pa.f32_env_stride = P(f32s) + t, T
             if pop is not None:
                 _abi.check(L.lnw_policy_act_pop(C.byref(pa), C.byref(pop), stream))
             else:
                 _abi.check(L.lnw_policy_act(C.byref(pa), stream))
-            if red_actor_rows:
+            if other_rows:
                 ra = PolicyArgs()
-                ra.obs, ra.E, ra.n, ra.D, ra.own0, ra.A = P(g.obs_red), E, nr, Dr, nb, A
-                ra.params, ra.bn_running = P(rap), int(self.red_bn == "running")
+                ra.obs, ra.E, ra.n, ra.D, ra.own0, ra.A = P(obuf), E, on, oD, oown0, A
+                ra.params, ra.bn_running = P(oap), int(obn == "running")
                 if fa is not None:
-                    ra.forced, ra.forced_act, ra.fa_env_stride = 1, P(fa) + (t * A + nb) * 4 * f4, T * A * 4
-                ra.seed, ra.call_dev, ra.T, ra.t, ra.which = seed, P(self._call), T, t, 2
-                ra.row_base, ra.alive, ra.full = g.env_id_base * nr, alive_p, P(full)
+                    ra.forced, ra.forced_act, ra.fa_env_stride = 1, P(fa) + (t * A + oown0) * 4 * f4, T * A * 4
+                ra.seed, ra.call_dev, ra.T, ra.t, ra.which = seed, P(self._call), T, t, owhich
+                ra.row_base, ra.alive, ra.full = g.env_id_base * on, alive_p, P(full)
                 _abi.check(L.lnw_policy_act(C.byref(ra), stream))
             if self.record_actions:
                 b["step_actions"][:, t] = full
                 b["step_kinds"][:, t] = kinds
             out = g.step(full, kinds, obs=not direct)
             pp = RolloutPostArgs()
-            pp.obs, pp.obs_env_stride, pp.E, pp.n, pp.D = pa.obs_out, T * nb * Db, E, nb, Db
+            pp.obs, pp.obs_env_stride, pp.E, pp.n, pp.D = pa.obs_out, T * n * D, E, n, D
             if cp is not None:
                 pp.critic, pp.val, pp.val_env_stride = P(cp), P(val) + t * f4, T
-            pp.rew, pp.rew_f64, pp.n_rew = P(out["rew_blue"]), rew_f64, nb
-            pp.rew_out, pp.rew_env_stride = P(rew) + t * nb * f8, T * nb
+            pp.rew, pp.rew_f64, pp.n_rew = P(rew_side), rew_f64, n
+            pp.rew_out, pp.rew_env_stride = P(rew) + t * n * f8, T * n
             pp.done, pp.live = P(out["done"]), P(live)
             pp.running, pp.running_env_stride = P(running) + t, T
             pp.stop_at_done = int(bool(self.stop_at_done))
@@ -740,19 +839,24 @@ class Rollout:
         self._call += 1
         rtg = reference_rtg(rew, self.gamma)
         b["rtg"] = rtg
+        if red_side:
+            b["sampled"] = running & (torch.arange(T, device=dev) >= self.warmup)[None]
         return b
 
     def _run_torch(self, generator, forced_actions, on_step):
         from ._abi import F_ALIVE, LNW_KIND_F32, LNW_KIND_F64
         g = self.g
-        E, nb, nr, A, D = g.E, g.nb, g.nr, g.A, g.Db
+        E, nb, nr, A = g.E, g.nb, g.nr, g.A
         dev = g.device
         T = self.T
+        red_side = self.side == "red"
+        # the learning side: its ships n, row length D, agent slots [own0, own0 + n)
+        _, n, D, own0, which, lbn = self._learning()
         b = self._buffers()
         obs, acts, logp, rew, val, running, f32_step = (b[k] for k in (
             "obs", "actions", "log_probs", "rewards", "values", "running", "f32_step"))
         full = torch.zeros((E, A, 4), dtype=torch.float64, device=dev)
-        red_actor_rows = self.red != "script" and self.red_actor is not None
+        other_rows = red_side or (self.red != "script" and self.red_actor is not None)
         if self.observe == "step":
             g.observe(-1)
         live = torch.ones(E, dtype=torch.bool, device=dev)
@@ -760,75 +864,98 @@ class Rollout:
         call = self._call  # device counter; keyed draws read it on the host here
 
         def draws(t, which, n_side):
-            """keyed draws for this step: which 0/1 blue sample / noise, 2 red"""
+            """keyed draws for this step: which 0/1 blue sample / noise, 2/3 red"""
             if self.keyed_seed is None:
                 return None
             slot = ((int(call.item()) * T + t) * 4 + which)
             return keyed_normal(base * n_side, E * n_side, 4, self.keyed_seed, slot, dev)
 
-        # the blue actor of every row: the module, or each member's own copy
+        # the learning actor of every row: the module, or each member's own copy
         # for the member's rows (a population / a flat `theta`)
         members = self._member_actors(int(self.keyed_seed if self.keyed_seed is not None else self.seed))
 
-        def blue(fn, *rows):
+        def learner(fn, *rows):
             """fn(actor, *rows) -> tuple of [rows, ...] tensors, over the members"""
             if members is None:
-                return fn(self.actor, *rows)
+                return fn(self._learning()[0], *rows)
             Gm, nets = members
-            parts = [fn(net, *[None if x is None else x[k * Gm * nb:(k + 1) * Gm * nb] for x in rows])
+            parts = [fn(net, *[None if x is None else x[k * Gm * n:(k + 1) * Gm * n] for x in rows])
                      for k, net in enumerate(nets)]
             return tuple(torch.cat(c) for c in zip(*parts))
 
         if self.G is not None:
             b["member"] = torch.arange(E, dtype=torch.int64, device=dev) // self.G + base // self.G
+        if self.record_actions:
+            b["step_actions"] = torch.zeros((E, T, A, 4), dtype=torch.float64, device=dev)
+            b["step_kinds"] = torch.zeros((E, T, A), dtype=torch.uint8, device=dev)
+        zero = torch.zeros((), device=dev)
         for t in range(T):
             if self.observe == "fresh":
                 g.observe(-1)
-            cur, cur_red = g.obs_blue, g.obs_red
+            cur, cur_other = (g.obs_red, g.obs_blue) if red_side else (g.obs_blue, g.obs_red)
             alive = g.get(F_ALIVE).t().bool()  # [E, A], slots not None
-            ab = alive[:, :nb, None]
+            al = alive[:, own0:own0 + n, None]
             # rows an env fills after its episode ended stay zero, as the
             # reference's buffers do after its `break` (ppo.py:640-641)
-            keep = ab & live[:, None, None] if self.stop_at_done else ab
-            obs[:, t] = torch.where(live[:, None, None], cur, torch.zeros((), device=dev)) \
-                if self.stop_at_done else cur
-            if forced_actions is not None:
-                a = forced_actions[:, t, :nb].to(torch.float32)
-                lp, _ = blue(lambda net, x, fa: net.get_dist(x, fa, bn=self.bn),
-                             cur.reshape(E * nb, D), a.reshape(E * nb, 4))
+            keep = al & live[:, None, None] if self.stop_at_done else al
+            obs[:, t] = torch.where(live[:, None, None], cur, zero) if self.stop_at_done else cur
+            scripted = t < self.warmup  # (side red) the learning side's own rows from the profiles
+            rows64 = None
+            if scripted:
+                rows64 = red_script_actions(self.table, t, n)  # [n, 4] float64
+                a = rows64.to(torch.float32)[None].expand(E, n, 4)
+                lp, _ = learner(lambda net, x, fa: net.get_dist(x, fa, bn=lbn),
+                                cur.reshape(E * n, D), a.reshape(E * n, 4))
+            elif forced_actions is not None:
+                a = forced_actions[:, t, own0:own0 + n].to(torch.float32)
+                lp, _ = learner(lambda net, x, fa: net.get_dist(x, fa, bn=lbn),
+                                cur.reshape(E * n, D), a.reshape(E * n, 4))
             else:
-                a, lp, _ = blue(lambda net, x, eps, neps: net(x, noise=self.noise, bn=self.bn, generator=generator,
-                                                              eps=eps, noise_eps=neps),
-                                cur.reshape(E * nb, D), draws(t, 0, nb),
-                                draws(t, 1, nb) if self.noise is not None else None)
-            a = torch.where(ab, a.reshape(E, nb, 4), torch.zeros((), device=dev))
-            acts[:, t] = torch.where(keep, a, torch.zeros((), device=dev))
-            logp[:, t] = torch.where(keep, lp.reshape(E, nb, 4), torch.zeros((), device=dev))
-            full[:, :nb] = a
-            ar = alive[:, nb:, None]
-            if self.red == "script":
-                full[:, nb:] = torch.where(ar, red_script_actions(self.table, t, nr),
-                                           torch.zeros((), dtype=torch.float64, device=dev))
-            elif self.red_actor is not None:
+                a, lp, _ = learner(lambda net, x, eps, neps: net(x, noise=self.noise, bn=lbn, generator=generator,
+                                                                 eps=eps, noise_eps=neps),
+                                   cur.reshape(E * n, D), draws(t, which, n),
+                                   draws(t, which + 1, n) if self.noise is not None else None)
+            a = torch.where(al, a.reshape(E, n, 4), zero)
+            acts[:, t] = torch.where(keep, a, zero)
+            logp[:, t] = torch.where(keep, lp.reshape(E, n, 4), zero)
+            # the step takes the profiles' float64 rows themselves, not the rounded ones
+            full[:, own0:own0 + n] = a if rows64 is None else torch.where(
+                al, rows64, torch.zeros((), dtype=torch.float64, device=dev))
+            if red_side:  # the frozen blue actor
+                ab = alive[:, :nb, None]
                 if forced_actions is not None:
-                    ra = forced_actions[:, t, nb:].to(torch.float32)
+                    ba = forced_actions[:, t, :nb].to(torch.float32)
                 else:
-                    ra, _, _ = self.red_actor(cur_red.reshape(E * nr, g.Dr), bn=self.red_bn,
-                                              generator=generator, eps=draws(t, 2, nr))
-                full[:, nb:] = torch.where(ar, ra.reshape(E, nr, 4),
-                                           torch.zeros((), device=dev)).double()
+                    ba, _, _ = self.actor(cur_other.reshape(E * nb, g.Db), bn=self.bn,
+                                          generator=generator, eps=draws(t, 0, nb))
+                full[:, :nb] = torch.where(ab, ba.reshape(E, nb, 4), zero).double()
             else:
-                full[:, nb:] = 0
+                ar = alive[:, nb:, None]
+                if self.red == "script":
+                    full[:, nb:] = torch.where(ar, red_script_actions(self.table, t, nr),
+                                               torch.zeros((), dtype=torch.float64, device=dev))
+                elif self.red_actor is not None:
+                    if forced_actions is not None:
+                        ra = forced_actions[:, t, nb:].to(torch.float32)
+                    else:
+                        ra, _, _ = self.red_actor(cur_other.reshape(E * nr, g.Dr), bn=self.red_bn,
+                                                  generator=generator, eps=draws(t, 2, nr))
+                    full[:, nb:] = torch.where(ar, ra.reshape(E, nr, 4), zero).double()
+                else:
+                    full[:, nb:] = 0
             # np.asarray(actions_for_step): float32 only if every row is float32
-            f32 = alive.all(1) if red_actor_rows else torch.zeros(E, dtype=torch.bool, device=dev)
+            f32 = alive.all(1) if other_rows and not scripted else torch.zeros(E, dtype=torch.bool, device=dev)
             f32_step[:, t] = f32
             kinds = torch.where(f32, LNW_KIND_F32, LNW_KIND_F64).to(torch.uint8)[:, None]
             if self.critic is not None:
-                v = self.critic(cur.reshape(E, nb * D)).reshape(E)
-                val[:, t] = torch.where(live, v, torch.zeros((), device=dev)) if self.stop_at_done else v
+                v = self.critic(cur.reshape(E, n * D)).reshape(E)
+                val[:, t] = torch.where(live, v, zero) if self.stop_at_done else v
+            if self.record_actions:
+                b["step_actions"][:, t] = full
+                b["step_kinds"][:, t] = kinds
             out = g.step(full, kinds.expand(E, A).contiguous())
             running[:, t] = live
-            r = out["rew_blue"].to(torch.float64)
+            r = out["rew_red" if red_side else "rew_blue"].to(torch.float64)
             rew[:, t] = torch.where(live[:, None], r, torch.zeros_like(r)) if self.stop_at_done else r
             if self.stop_at_done:
                 live = live & (out["done"] != 0)
@@ -838,6 +965,8 @@ class Rollout:
         # the learner's advantage is gae(rtg, values) on a sampled minibatch
         # (ppo.py:336), left to the caller as in the reference
         b["rtg"] = reference_rtg(rew, self.gamma)
+        if red_side:
+            b["sampled"] = running & (torch.arange(T, device=dev) >= self.warmup)[None]
         return b
 
     def capture(self, generator=None):
