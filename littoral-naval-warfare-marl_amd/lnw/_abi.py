@@ -271,6 +271,17 @@ def load(path=None):
     return L
 
 
+def stream(device):
+    """The current stream of a device as the kernels' stream argument."""
+    import torch  # (not at the top: lnw.build and lnw.config load without torch)
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def check_impl(impl):
+    if impl not in ("hip", "torch"):
+        raise ValueError("impl must be 'hip' or 'torch'")
+
+
 def check(rc):
     if rc != 0:
         msg = _lib.lnw_last_error().decode() if _lib is not None else "?"

@@ -29,7 +29,8 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import dist
+from . import _abi, dist
+from .keyed import cached
 
 MAX_RANKS = 64  # include/lnw.h: lnw_ppo_sample_merge
 
@@ -56,10 +57,6 @@ def message(b, row_base, status):
                       status.to(b["index"].device, torch.int64).reshape(1)])
 
 
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 def merge_buffers(batch, device):
     e = lambda dtype: torch.empty(batch, dtype=dtype, device=device)  # noqa: E731
     return dict(key=e(torch.float64), global_row=e(torch.int64), src_rank=e(torch.int32), src_pos=e(torch.int32),
@@ -79,14 +76,13 @@ def merge(lists, batch, n, impl="hip", out=None):
         raise ValueError("a message holds 2 batch + 1 words; n >= 1")
     m = merge_buffers(B, lists.device) if out is None else out
     if impl == "hip":
-        from . import _abi
         L = _abi.load()
         lists = lists.contiguous()
         a = _abi.PpoMergeArgs()
         a.lists, a.W, a.n, a.stride, a.batch = lists.data_ptr(), W, n, stride, B
         a.key_out, a.row_out, a.index_out = m["key"].data_ptr(), m["global_row"].data_ptr(), m["index"].data_ptr()
         a.src_rank, a.src_pos, a.status_out = m["src_rank"].data_ptr(), m["src_pos"].data_ptr(), m["status"].data_ptr()
-        _abi.check(L.lnw_ppo_sample_merge(C.byref(a), _stream(lists.device)))
+        _abi.check(L.lnw_ppo_sample_merge(C.byref(a), _abi.stream(lists.device)))
         return m
     h = lists.detach().cpu().numpy()
     key = np.ascontiguousarray(h[:, :B]).view(np.float64).reshape(-1)
@@ -112,7 +108,6 @@ def pack(ro, merged, rank, row_base, impl="hip", xbuf=None):
     if row_base % n:
         raise ValueError("row_base must be a whole number of groups")
     if impl == "hip":
-        from . import _abi
         L = _abi.load()
         words = L.lnw_ppo_pack_words(B, n, D)
         if words <= 0:
@@ -125,7 +120,7 @@ def pack(ro, merged, rank, row_base, impl="hip", xbuf=None):
         a.n, a.D, a.rank, a.batch = n, D, int(rank), B
         a.row_out, a.src_rank = merged["global_row"].data_ptr(), merged["src_rank"].data_ptr()
         a.xbuf, a.xbuf_words = xbuf.data_ptr(), xbuf.numel()
-        _abi.check(L.lnw_ppo_rows_pack(C.byref(a), _stream(obs.device)))
+        _abi.check(L.lnw_ppo_rows_pack(C.byref(a), _abi.stream(obs.device)))
         return xbuf
     words = pack_words(B, n, D)
     if xbuf is None:
@@ -155,6 +150,22 @@ def unpack(xbuf, merged, n, D):
                 key=merged["key"], global_row=merged["global_row"])
 
 
+def exchange(local, status, row_base, batch, n, impl, group, merge_out, pack_owned):
+    """The ranks' part of a sharded draw, after the local draw `local` (its
+    count of non-finite rows in `status`): one all-gather of the messages, the
+    merge into merge_out (merge_buffers; its status becomes `status`, so the
+    count over all ranks replaces the local one), pack_owned(merged, rank) ->
+    this rank's exchange buffer, and one int32 SUM all-reduce of it. Returns
+    (merged, the summed buffer)."""
+    merge_out["status"] = status
+    rank, _ = dist.rank_size(group)
+    lists = dist.all_gather(message(local, row_base, status), group)
+    merged = merge(lists, batch, n, impl, out=merge_out)
+    xbuf = pack_owned(merged, rank)
+    dist.all_reduce_sum_(xbuf, group)
+    return merged, xbuf
+
+
 def minibatch_dist(learner, out, batch, row_base, seed=None, rtg=None, advance=True, group=None):
     """PPOLearner.minibatch_dist (its docstring has the contract)."""
     B = int(batch)
@@ -163,15 +174,9 @@ def minibatch_dist(learner, out, batch, row_base, seed=None, rtg=None, advance=T
     # the local draw: raises on batch > local rows, before any collective
     local = learner.minibatch(out, B, seed=seed, rtg=rtg, row_base=row_base, advance=advance)
     ro = learner.rollout_rows(out, rtg)
-    rank, W = dist.rank_size(group)
-    lists = dist.all_gather(message(local, row_base, learner.sample_status), group)
-    buf = learner._dist_buf.get((B, ro["n"], ro["D"]))
-    if buf is None:
-        buf = merge_buffers(B, learner.device)
-        buf["status"] = learner.sample_status  # the global count replaces the local one
-        buf["xbuf"] = torch.empty(pack_words(B, ro["n"], ro["D"]), dtype=torch.int32, device=learner.device)
-        learner._dist_buf[(B, ro["n"], ro["D"])] = buf
-    merged = merge(lists, B, ro["n"], learner.impl, out=buf)
-    xbuf = pack(ro, merged, rank, row_base, learner.impl, xbuf=buf["xbuf"])
-    dist.all_reduce_sum_(xbuf, group)
-    return unpack(xbuf, merged, ro["n"], ro["D"])
+    n, D, dev = ro["n"], ro["D"], learner.device
+    buf = cached(learner._dist_buf, (B, n, D), lambda: dict(
+        merge_buffers(B, dev), xbuf=torch.empty(pack_words(B, n, D), dtype=torch.int32, device=dev)))
+    merged, xbuf = exchange(local, learner.sample_status, row_base, B, n, learner.impl, group, buf,
+                            lambda m, rank: pack(ro, m, rank, row_base, learner.impl, xbuf=buf["xbuf"]))
+    return unpack(xbuf, merged, n, D)

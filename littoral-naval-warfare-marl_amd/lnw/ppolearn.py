@@ -8,65 +8,27 @@ rows as the sequence), ppo.py:716-729 (popart_normalize), ppo.py:342-362 (the
 two losses), ppo.py:371-380 (clip_grad_norm_ and Adam per network),
 ppo.py:311-319 (the prioritised sampler). The kernels are csrc/lnw_ppolearn.hip
 (lnw_ppo_grad, lnw_ppo_clip_adam), csrc/lnw_pposample.hip (lnw_ppo_sample,
-the keyed minibatch draw behind PPOLearner.minibatch) and csrc/lnw_ppodist.hip
-(the merge and the row exchange behind PPOLearner.minibatch_dist, which trains
-on rollouts sharded over ranks: lnw/ppodist.py). learn()'s outer schedule
+the keyed minibatch draw behind PPOLearner.minibatch: lnw/keyed.py, with its
+host restatement sample_keys) and csrc/lnw_ppodist.hip (the merge and the row
+exchange behind PPOLearner.minibatch_dist, which trains on rollouts sharded
+over ranks: lnw/ppodist.py). The flat layouts are lnw/layout.py's
+(actor_slices, critic_slices, pack). learn()'s outer schedule
 (noise ratio, lr halving on victories, epoch count) stays with the caller;
 parameter noise is the rollout's (lnw.rollout.Rollout(param_noise=..., theta=
 learner.theta_actor) acts from this learner's flat vector).
 """
 import ctypes as C
+from functools import partial
 
-import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 from torch.distributions import Normal
 
-from .rollout import WINDOW
-
-CONV_PARAMS = 578
-ACTOR_NAMES = ("conv1.weight", "conv1.bias", "norm1.weight", "norm1.bias", "norm1.running_mean",
-               "norm1.running_var", "conv2.weight", "conv2.bias", "norm2.weight", "norm2.bias",
-               "norm2.running_mean", "norm2.running_var", "convhead.weight", "convhead.bias",
-               "layernorm.weight", "layernorm.bias", "fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias",
-               "fc3.weight", "fc3.bias", "normal_head.weight", "log_std_head.weight", "logstd")
-CRITIC_NAMES = ("fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias", "fc3.weight", "fc3.bias", "fc4.weight",
-                "fc4.bias")
-RUNNING = ("norm1.running_mean", "norm1.running_var", "norm2.running_mean", "norm2.running_var")
-
-
-def _slices(names, shapes):
-    out, k = {}, 0
-    for name, shp in zip(names, shapes):
-        out[name] = (k, tuple(shp))
-        k += int(np.prod(shp))
-    return out
-
-
-def actor_slices(n_in):
-    """{state_dict name: (offset, shape)} of the actor's flat layout
-    (include/lnw.h): BatchedActor.packed_features()'s order, then fc1 / fc2 / fc3
-    weight and bias, normal_head, log_std_head and a slot for logstd."""
-    return _slices(ACTOR_NAMES, ((5, 1, 3, 3), (5,), (5,), (5,), (5,), (5,), (8, 5, 3, 3), (8,), (8,), (8,), (8,),
-                                 (8,), (12, 8), (12,), (n_in,), (n_in,), (64, n_in), (64,), (64, 64), (64,),
-                                 (32, 64), (32,), (4, 32), (4, 32), ()))
-
-
-def critic_slices(n, D):
-    """{state_dict name: (offset, shape)} of the critic's flat layout: the
-    state_dict order."""
-    return _slices(CRITIC_NAMES, ((32, n * D), (32,), (64, 32), (64,), (64, 64), (64,), (1, 64), (1,)))
-
-
-def flat_size(sl):
-    return max(k + int(np.prod(s)) for k, s in sl.values())
-
-
-def pack(module, sl):
-    """The module's parameters and running statistics as a flat float32 vector."""
-    sd = module.state_dict()
-    return torch.cat([sd[name].detach().reshape(-1).float() for name in sl]).contiguous()
+from . import _abi, keyed, layout
+from .keyed import _p_log, _philox10, sample_keys  # noqa: F401  (the draw's host restatement lives there)
+from .layout import (ACTOR_NAMES, CONV_PARAMS, CRITIC_NAMES, RUNNING, WINDOW, actor_slices,  # noqa: F401
+                     critic_slices, flat_size, pack)
 
 
 def actor_forward(theta, obs, actions, sl):
@@ -74,10 +36,7 @@ def actor_forward(theta, obs, actions, sl):
     BatchNorm statistics, from a flat parameter vector (differentiable in
     theta): log-probabilities [B, 4], entropies [B, 4], and the rows'
     statistics [B, 26] (13 channel means, then their unbiased variances)."""
-    def seg(name):
-        k, shp = sl[name]
-        return theta[k:k + int(np.prod(shp))].reshape(shp)
-
+    seg = partial(layout.seg, theta, sl)
     B = obs.shape[0]
     z = obs[:, :WINDOW].reshape(B, 1, 7, 7)
     z1 = F.conv2d(z, seg("conv1.weight"), seg("conv1.bias"), padding=1)
@@ -99,10 +58,7 @@ def actor_forward(theta, obs, actions, sl):
 
 def critic_forward(theta, gs, sl):
     """Value.forward (network.py:168-175) from a flat parameter vector: [B]."""
-    def seg(name):
-        k, shp = sl[name]
-        return theta[k:k + int(np.prod(shp))].reshape(shp)
-
+    seg = partial(layout.seg, theta, sl)
     x = torch.tanh(F.linear(gs, seg("fc1.weight"), seg("fc1.bias")))
     x = torch.tanh(F.linear(x, seg("fc2.weight"), seg("fc2.bias")))
     x = torch.tanh(F.linear(x, seg("fc3.weight"), seg("fc3.bias")))
@@ -162,49 +118,6 @@ def running_after(r0, stats, momentum=0.1):
     return (1.0 - momentum) ** B * r0.double() + momentum * (wgt[:, None] * stats.double()).sum(0)
 
 
-def _philox10(c, k0, k1):
-    """Philox4x32-10 on uint64 arrays that hold 32-bit words (lnw_device.h)."""
-    m32 = np.uint64(0xFFFFFFFF)
-    c0, c1, c2, c3 = c
-    for _ in range(10):
-        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
-        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & m32, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & m32
-        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & m32, (k1 + np.uint64(0xBB67AE85)) & m32
-    return c0, c1, c2, c3
-
-
-def _p_log(x):
-    """lnw_device.h's portable ln in float64 array operations: the same bits."""
-    m, e = np.frexp(x)
-    low = m < 0.70710678118654752
-    m = np.where(low, m * 2.0, m)
-    e = e - low
-    s = (m - 1.0) / (m + 1.0)
-    z = s * s
-    p = np.full_like(z, 1.0 / 19.0)
-    for d in (17.0, 15.0, 13.0, 11.0, 9.0, 7.0, 5.0, 3.0, 1.0):
-        p = p * z + 1.0 / d
-    return 2.0 * s * p + e.astype(np.float64) * 0.6931471805599453
-
-
-def sample_keys(rtg, seed, slot, row_base=0):
-    """lnw_ppo_sample's keys (include/lnw.h) of a float32 reward-to-go vector on
-    the host: float64 [rows], +inf where rtg is not finite."""
-    from ._abi import LNW_SAMPLE_CTR2, LNW_SAMPLE_CTR3
-    rtg = np.ascontiguousarray(rtg, np.float32).reshape(-1)
-    m32 = np.uint64(0xFFFFFFFF)
-    ctr = np.uint64(int(slot) << 40) + np.uint64(int(row_base)) + np.arange(rtg.shape[0], dtype=np.uint64)
-    seed = int(seed) & (2 ** 64 - 1)
-    o = _philox10((ctr & m32, ctr >> np.uint64(32), np.full_like(ctr, LNW_SAMPLE_CTR2),
-                   np.full_like(ctr, LNW_SAMPLE_CTR3)), np.uint64(seed & 0xFFFFFFFF), np.uint64(seed >> 32))
-    u = ((o[0] >> np.uint64(5)).astype(np.float64) * 67108864.0
-         + (o[1] >> np.uint64(6)).astype(np.float64)) / 9007199254740992.0
-    with np.errstate(all="ignore"):
-        w = (np.abs(rtg) + np.float32(1e-5)).astype(np.float64)
-        key = -_p_log(1.0 - u) / w + 0.0
-    return np.where(np.isfinite(rtg), key, np.inf)
-
-
 class PPOLearner:
     """PPO.learn's minibatch update (ppo.py:321-390) for one side (blue, or red
     given the red actor and critic and a Rollout(side="red")'s buffers) on flat
@@ -235,8 +148,7 @@ class PPOLearner:
 
     def __init__(self, actor, critic, lr=1e-4, eps_clip=0.2, entropy_coef=0.2, gamma=0.99, lambda_=0.95,
                  max_grad_norm=1.0, betas=(0.9, 0.999), eps=1e-8, impl="hip", device=None, sample_seed=0):
-        if impl not in ("hip", "torch"):
-            raise ValueError("impl must be 'hip' or 'torch'")
+        _abi.check_impl(impl)
         if device is None:
             device = "cuda" if impl == "hip" else next(actor.parameters()).device
         self.device = dev = torch.device(device)
@@ -325,14 +237,14 @@ class PPOLearner:
         definition with NumPy on the host (it reads the counter, so it
         synchronises), the same index bit for bit."""
         ro = self.rollout_rows(out, rtg)
-        N, B = ro["rtg"].shape[0], int(batch)
-        from ._abi import LNW_SAMPLE_MAX_BATCH
-        if not 1 <= B <= min(N, LNW_SAMPLE_MAX_BATCH):
-            raise ValueError(f"batch must be in 1 .. min(rows, {LNW_SAMPLE_MAX_BATCH})")
-        seed = (self.sample_seed if seed is None else int(seed)) & (2 ** 64 - 1)
-        draw = self._sample_hip if self.impl == "hip" else self._sample_torch
-        b = draw(ro["rtg"], ro["actions"], ro["log_probs"], ro["values"], ro["n"], B, seed, int(row_base),
-                 bool(advance))
+        N = ro["rtg"].shape[0]
+        B = keyed.check_batch(batch, N)
+        buf = None  # (the torch arm returns new tensors)
+        if self.impl == "hip":
+            buf = keyed.cached(self._sample_buf, (N, B),
+                               lambda: keyed.draw_buffers(N, B, self.device, "hip", payload=True))
+        b = keyed.draw(ro["rtg"], B, self.sample_seed if seed is None else seed, self.draw, self.sample_status,
+                       row_base, advance, self.impl, buf, payload=ro)
         return dict(obs=ro["obs"], index=b["index"], actions=b["actions"], old_log_probs=b["old_log_probs"],
                     rtg=b["rtg"], old_values=b["old_values"], key=b["key"])
 
@@ -379,46 +291,6 @@ class PPOLearner:
         from . import ppodist
         return ppodist.minibatch_dist(self, out, batch, row_base, seed=seed, rtg=rtg, advance=advance, group=group)
 
-    def _sample_hip(self, rtg, acts, lps, vals, n, B, seed, row_base, advance):
-        from . import _abi
-        L = _abi.load()
-        dev = self.device
-        N = rtg.shape[0]
-        buf = self._sample_buf.get((N, B))
-        if buf is None:
-            need = L.lnw_ppo_sample_workspace_bytes(N, B)
-            if need <= 0:
-                raise _abi.LnwError(f"lnw_ppo_sample does not support rows={N}, batch={B}")
-            e = lambda *s, dtype=torch.float32: torch.empty(s, dtype=dtype, device=dev)  # noqa: E731
-            buf = dict(index=e(B, dtype=torch.int64), key=e(B, dtype=torch.float64), actions=e(B, 4),
-                       old_log_probs=e(B, 4), rtg=e(B), old_values=e(B), ws=e(need, dtype=torch.uint8))
-            self._sample_buf[(N, B)] = buf
-        a = _abi.PpoSampleArgs()
-        a.rtg, a.rows, a.row_base, a.batch, a.seed = rtg.data_ptr(), N, row_base, B, seed
-        a.draw_dev, a.advance = self.draw.data_ptr(), int(advance)
-        a.actions, a.log_probs, a.values, a.n = acts.data_ptr(), lps.data_ptr(), vals.data_ptr(), n
-        a.index_out, a.key_out = buf["index"].data_ptr(), buf["key"].data_ptr()
-        a.actions_out, a.log_probs_out = buf["actions"].data_ptr(), buf["old_log_probs"].data_ptr()
-        a.rtg_out, a.old_values_out = buf["rtg"].data_ptr(), buf["old_values"].data_ptr()
-        a.status = self.sample_status.data_ptr()
-        a.workspace, a.workspace_bytes = buf["ws"].data_ptr(), buf["ws"].numel()
-        _abi.check(L.lnw_ppo_sample(C.byref(a), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-        return buf
-
-    def _sample_torch(self, rtg, acts, lps, vals, n, B, seed, row_base, advance):
-        dev = self.device
-        r = rtg.detach().cpu().numpy()
-        key = sample_keys(r, seed, int(self.draw), row_base)
-        # ascending key, ties to the lower row (keys compare as numbers: sample_keys holds no -0)
-        order = np.lexsort((np.arange(key.shape[0]), key))[:B]
-        index = torch.from_numpy(order.astype(np.int64)).to(dev)
-        self.sample_status.fill_(int((~np.isfinite(r)).sum()))
-        if advance:
-            self.draw += 1
-        return dict(index=index, key=torch.from_numpy(key[order]).to(dev), actions=acts[index].contiguous(),
-                    old_log_probs=lps[index].contiguous(), rtg=rtg[index].contiguous(),
-                    old_values=vals[torch.div(index, n, rounding_mode="floor")].contiguous())
-
     def _batch(self, b):
         dev = self.device
         f = lambda t: t.to(dev, torch.float32).contiguous()  # noqa: E731
@@ -434,7 +306,6 @@ class PPOLearner:
 
     # ---- HIP arm ---------------------------------------------------------------------
     def _grad_hip(self, b, want, freeze):
-        from . import _abi
         L = _abi.load()
         dev = self.device
         B = b["rtg"].shape[0]
@@ -462,13 +333,12 @@ class PPOLearner:
             a.new_log_probs, a.entropies = out["new_log_probs"].data_ptr(), out["entropies"].data_ptr()
             a.values, a.advantage = out["values"].data_ptr(), out["advantage"].data_ptr()
         a.workspace, a.workspace_bytes = self._ws.data_ptr(), self._ws.numel()
-        _abi.check(L.lnw_ppo_grad(C.byref(a), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        _abi.check(L.lnw_ppo_grad(C.byref(a), _abi.stream(dev)))
         return out
 
     def _adam_hip(self):
-        from . import _abi
         L = _abi.load()
-        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        st = _abi.stream(self.device)
         for k, (th, g, m, v, cnt) in enumerate(((self.theta_actor, self._grad_actor, self.m_actor, self.v_actor,
                                                  self.step_actor),
                                                 (self.theta_critic, self._grad_critic, self.m_critic, self.v_critic,
@@ -570,11 +440,8 @@ class PPOLearner:
         back into the BatchedActor / BatchedCritic modules, on the device they
         live on (device-to-device copies: no host round trip); returns (actor,
         critic). The next Rollout.run() acts with the updated weights."""
-        for net, theta, sl in ((self.actor, self.theta_actor, self.actor_sl),
-                               (self.critic, self.theta_critic, self.critic_sl)):
-            sd = net.state_dict()  # (tensors sharing the module's storage)
-            for name, (k, shp) in sl.items():
-                sd[name].copy_(theta[k:k + int(np.prod(shp))].reshape(shp))
+        layout.unpack_(self.actor, self.theta_actor, self.actor_sl)
+        layout.unpack_(self.critic, self.theta_critic, self.critic_sl)
         for nm in (self.actor.norm1, self.actor.norm2):
             nm.num_batches_tracked.copy_(self.nbt[0])
         return self.actor, self.critic

@@ -12,39 +12,25 @@ without replacement, uniformly or by priorities kept beside the ring
 """
 import ctypes as C
 import math
+from functools import partial
 
 import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import _abi, layout
 from .batched import BatchedGame
-from .rollout import WINDOW
+from .keyed import keyed_uniform4
+from .layout import CONV_PARAMS, N_ATTACK, N_MOVE, N_RADAR, PACKED_NAMES, WINDOW, packed_slices  # noqa: F401
 
-N_RADAR, N_ATTACK, N_MOVE = 2, 5, 50          # DMLP's heads (network.py:261-263)
 N_Q = N_RADAR + N_ATTACK + N_MOVE             # 57, in radar, attack, movement order
 HEADS = ((0, N_RADAR), (N_RADAR, N_RADAR + N_ATTACK), (N_RADAR + N_ATTACK, N_Q))
-CONV_PARAMS = 578                             # the conv head's packed floats (csrc/lnw_convhead.inc)
 
 
 def epsilon(t, start, end, decay):
     """ddqn.py:149-151 `get_epsilon`: end + (start - end) * exp(-t / decay)."""
     return end + (start - end) * math.exp(-1. * t / decay)
-
-
-def keyed_uniform4(row0, rows, seed, slot, device):
-    """The four keyed uniforms [rows, 4] of global rows row0 .. row0+rows-1 that
-    lnw_qnet_act draws: Philox (lnw_fill_uniform_f32) at absolute offset
-    slot * 2^40 + 4 * row — keyed_normal's convention (lnw/rollout.py), so a
-    shard of the envs draws what one call over all envs draws for them."""
-    from . import _abi
-    L = _abi.load()
-    u = torch.empty((rows, 4), dtype=torch.float32, device=device)
-    if rows:
-        _abi.check(L.lnw_fill_uniform_f32(u.data_ptr(), rows * 4, int(seed) & (2**64 - 1),
-                                          (int(slot) << 40) + 4 * int(row0),
-                                          torch.cuda.current_stream(device).cuda_stream))
-    return u
 
 
 def random_rows(u):
@@ -112,28 +98,16 @@ class BatchedQNet(nn.Module):
         """Every parameter lnw_qnet_act reads (csrc/lnw_qnet.hip), in its order:
         the conv head in lnw_actor_features' order (578 floats), then W [57][n_in]
         with the rows in radar, attack, movement order, then b [57]."""
-        return torch.cat([p.detach().reshape(-1).float() for p in self._pack_order()]).contiguous()
-
-    def _pack_order(self):
-        return [self.conv1.weight, self.conv1.bias, self.norm1.weight, self.norm1.bias,
-                self.norm1.running_mean, self.norm1.running_var, self.conv2.weight,
-                self.conv2.bias, self.norm2.weight, self.norm2.bias, self.norm2.running_mean,
-                self.norm2.running_var, self.convhead.weight, self.convhead.bias,
-                self.radar.weight, self.attack.weight, self.movement.weight,
-                self.radar.bias, self.attack.bias, self.movement.bias]
+        return layout.pack(self, packed_slices(self.n_in))
 
     @torch.no_grad()
     def unpack_(self, flat):
         """The inverse of packed(): load a flat vector in its layout into the
         parameters and running statistics, in place."""
-        parts = self._pack_order()
-        if flat.numel() != sum(p.numel() for p in parts):
+        sl = packed_slices(self.n_in)
+        if flat.numel() != layout.flat_size(sl):
             raise ValueError("flat vector length does not match packed()")
-        k = 0
-        for p in parts:
-            p.copy_(flat[k:k + p.numel()].reshape(p.shape).to(p.device, p.dtype))
-            k += p.numel()
-        return self
+        return layout.unpack_(self, flat, sl)
 
     @staticmethod
     def _bn(m, z, bn):
@@ -174,7 +148,6 @@ class BatchedQNet(nn.Module):
         tensor [E, n, D], or (device pointer, (E, n, D), device) for rows in
         caller memory (env e at pointer + e * obs_in_env_stride floats); alive:
         [A][E] uint8 tensor or a device pointer."""
-        from . import _abi
         L = _abi.load()
         if torch.is_tensor(obs):
             obs = obs.contiguous().float()
@@ -209,7 +182,7 @@ class BatchedQNet(nn.Module):
         if want_explored:
             out["explored"] = torch.empty((E * n,), dtype=torch.uint8, device=dev)
             a.explored = out["explored"].data_ptr()
-        _abi.check(L.lnw_qnet_act(C.byref(a), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        _abi.check(L.lnw_qnet_act(C.byref(a), _abi.stream(dev)))
         return out
 
     @torch.no_grad()
@@ -234,8 +207,7 @@ class BatchedQNet(nn.Module):
                              seed=seed, slot=slot, row_base=row_base, bn=bn, want_q=want_q, want_explored=True)
             o["explored"] = o["explored"].bool().reshape(E, n)
             return o
-        if impl != "torch":
-            raise ValueError("impl must be 'hip' or 'torch'")
+        _abi.check_impl(impl)
         q = self.q_torch(obs.reshape(E * n, D).float(), bn)
         greedy = torch.stack([q[:, lo:hi].argmax(1) for lo, hi in HEADS], 1).to(torch.int32)
         u = keyed_uniform4(row_base, E * n, seed, slot, dev)
@@ -264,7 +236,6 @@ class BatchedQNet(nn.Module):
 def red_random_act(game, full, t, seed, slot, live=None, act_out=None, act_env_stride=0, explored=None):
     """Untrained red's rows (ddqn.py:316-328) of every env, one lnw_qnet_act
     launch (LNW_QNET_RED_RANDOM) into `full` [E, A, 4] int32."""
-    from . import _abi
     L = _abi.load()
     g = game
     a = _abi.QnetArgs()
@@ -342,8 +313,7 @@ class QCollector:
             raise ValueError("side='red' needs a red BatchedQNet")
         if priority not in (None, "uniform", "reward"):
             raise ValueError("priority must be None, 'uniform' or 'reward'")
-        if impl not in ("hip", "torch"):
-            raise ValueError("impl must be 'hip' or 'torch'")
+        _abi.check_impl(impl)
         g = self.g = game
         self.blue_net, self.red, self.side, self.bn = blue_net, red, side, bn
         self.cap, self.seed = int(capacity), int(seed)
@@ -506,37 +476,12 @@ class QCollector:
                                      bool(advance), group, self.impl, self._replay_buf)
 
 
-# names of packed()'s segments, in its order (state_dict keys)
-PACKED_NAMES = ("conv1.weight", "conv1.bias", "norm1.weight", "norm1.bias", "norm1.running_mean",
-                "norm1.running_var", "conv2.weight", "conv2.bias", "norm2.weight", "norm2.bias",
-                "norm2.running_mean", "norm2.running_var", "convhead.weight", "convhead.bias",
-                "radar.weight", "attack.weight", "movement.weight", "radar.bias", "attack.bias",
-                "movement.bias")
-_RUNNING = ("norm1.running_mean", "norm1.running_var", "norm2.running_mean", "norm2.running_var")
-
-
-def packed_slices(n_in):
-    """{state_dict name: (offset, shape)} of packed()'s layout for n_in head inputs."""
-    shapes = ((5, 1, 3, 3), (5,), (5,), (5,), (5,), (5,), (8, 5, 3, 3), (8,), (8,), (8,), (8,), (8,),
-              (12, 8), (12,), (N_RADAR, n_in), (N_ATTACK, n_in), (N_MOVE, n_in), (N_RADAR,),
-              (N_ATTACK,), (N_MOVE,))
-    out, k = {}, 0
-    for name, shp in zip(PACKED_NAMES, shapes):
-        out[name] = (k, shp)
-        k += int(np.prod(shp))
-    return out
-
-
 def _flat_forward(theta, obs, bn, sl):
     """DMLP.forward from a flat parameter vector (differentiable in theta):
     q [B, 57] after the ReLU, and the batch mean / biased variance of the 13
     BatchNorm channels [2, 13]. bn: "batch" or "running" (the running slots are
     constants then)."""
-    def seg(name):
-        k, shp = sl[name]
-        t = theta[k:k + int(np.prod(shp))].reshape(shp)
-        return t.detach() if name in _RUNNING else t
-
+    seg = partial(layout.seg, theta, sl)
     B = obs.shape[0]
     stats = []
 
@@ -545,8 +490,8 @@ def _flat_forward(theta, obs, bn, sl):
         stats.append((mean.detach(), var.detach()))
         if bn == "batch":
             return F.batch_norm(z, None, None, seg(pre + ".weight"), seg(pre + ".bias"), True, 0.0, 1e-5)
-        return F.batch_norm(z, seg(pre + ".running_mean"), seg(pre + ".running_var"), seg(pre + ".weight"),
-                            seg(pre + ".bias"), False, 0.0, 1e-5)
+        return F.batch_norm(z, seg(pre + ".running_mean").detach(), seg(pre + ".running_var").detach(),
+                            seg(pre + ".weight"), seg(pre + ".bias"), False, 0.0, 1e-5)
 
     z = obs[:, :WINDOW].reshape(B, 1, 7, 7)
     z = F.max_pool2d(F.relu(norm(F.conv2d(z, seg("conv1.weight"), seg("conv1.bias"), padding=1), "norm1")), 2, 2)
@@ -584,8 +529,7 @@ class QLearner:
                  policy_bn="batch", impl="hip", device=None):
         if policy_bn not in ("batch", "running"):
             raise ValueError("policy_bn must be 'batch' or 'running'")
-        if impl not in ("hip", "torch"):
-            raise ValueError("impl must be 'hip' or 'torch'")
+        _abi.check_impl(impl)
         if device is None:
             device = "cuda" if impl == "hip" else next(policy.parameters()).device
         self.device = dev = torch.device(device)
@@ -636,7 +580,6 @@ class QLearner:
 
     # ---- HIP arm ---------------------------------------------------------------
     def _grad_hip(self, r, want, freeze):
-        from . import _abi
         L = _abi.load()
         dev = self.device
         B, D = r["state"].shape
@@ -660,16 +603,15 @@ class QLearner:
             out["stats"] = torch.empty((2, 2, 13), dtype=torch.float32, device=dev)
             a.y_out, a.qs_out, a.stats_out = out["y"].data_ptr(), out["qs"].data_ptr(), out["stats"].data_ptr()
         a.workspace, a.workspace_bytes = self._ws.data_ptr(), self._ws.numel()
-        _abi.check(L.lnw_qnet_grad(C.byref(a), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        _abi.check(L.lnw_qnet_grad(C.byref(a), _abi.stream(dev)))
         return out
 
     def _adam_hip(self):
-        from . import _abi
         L = _abi.load()
         _abi.check(L.lnw_qnet_adam(self.theta.data_ptr(), self._grad.data_ptr(), self.m.data_ptr(),
                                    self.v.data_ptr(), self.theta.numel(), self.step_count.data_ptr(),
                                    self.lr, self.betas[0], self.betas[1], self.eps, self.clamp,
-                                   C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+                                   _abi.stream(self.device)))
 
     # ---- torch arm ---------------------------------------------------------------
     def _update_running(self, theta, stats, B):

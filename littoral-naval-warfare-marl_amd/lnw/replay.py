@@ -16,6 +16,7 @@ cap, NaN for a slot that holds no transition yet.
   draw          lnw_ppo_sample over the flattened priorities: `batch` distinct
                 rows by weights |p| + 1e-5 in ascending (key, row) order; equal
                 priorities make it uniform sampling without replacement
+                (lnw.keyed.draw, the learner's draw without the payload)
   pack          the drawn transitions as 32-bit words: state, next_state,
                 action, reward, done per ship, zero words in the slots another
                 rank owns (lnw_replay_pack)
@@ -26,27 +27,18 @@ cap, NaN for a slot that holds no transition yet.
 
 impl="hip" runs on the device on the current stream with no host
 synchronisation; impl="torch" is the same definition without the library (the
-draw from lnw.ppolearn.sample_keys and np.lexsort, the pack by torch indexing on
+draw from lnw.keyed.sample_keys and np.lexsort, the pack by torch indexing on
 int32 views), on the host or the device, and gives the same bits.
 """
 import ctypes as C
 
-import numpy as np
 import torch
 
-from . import dist, ppodist
-from ._abi import LNW_SAMPLE_MAX_BATCH
+from . import _abi, ppodist
+from ._abi import check_impl
+from .keyed import cached, check_batch, draw, draw_buffers
 
 ROW_KEYS = ("state", "next_state", "action", "reward", "done")
-
-
-def _check_impl(impl):
-    if impl not in ("hip", "torch"):
-        raise ValueError("impl must be 'hip' or 'torch'")
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def ring_shape(ring):
@@ -64,19 +56,18 @@ def mark(priority, reward, k, mode, impl="hip"):
     """priority[:, k] for the transitions of ring slot k. mode "uniform": 1.0;
     "reward": sum over ships i = 0 .. n-1, in that order, in float32, of
     |float32(reward[k, e, i])|."""
-    _check_impl(impl)
+    check_impl(impl)
     if mode not in ("uniform", "reward"):
         raise ValueError("priority must be 'uniform' or 'reward'")
     E, cap = priority.shape
     n = reward.shape[2]
     if impl == "hip":
-        from . import _abi
         L = _abi.load()
         a = _abi.ReplayMarkArgs()
         a.priority, a.E, a.cap, a.k, a.n = priority.data_ptr(), E, cap, int(k), n
         if mode == "reward":
             a.reward, a.reward_f64 = reward.data_ptr(), int(reward.dtype == torch.float64)
-        _abi.check(L.lnw_replay_mark(C.byref(a), _stream(priority.device)))
+        _abi.check(L.lnw_replay_mark(C.byref(a), _abi.stream(priority.device)))
         return priority
     if mode == "uniform":
         priority[:, k] = 1.0
@@ -87,56 +78,6 @@ def mark(priority, reward, k, mode, impl="hip"):
         p = p + mag[:, i]
     priority[:, k] = p
     return priority
-
-
-def draw_buffers(rows, batch, device, impl="hip"):
-    """The outputs (and, for the kernels, the workspace) of one draw shape."""
-    e = lambda dtype: torch.empty(batch, dtype=dtype, device=device)  # noqa: E731
-    buf = dict(index=e(torch.int64), key=e(torch.float64))
-    if impl == "hip":
-        from . import _abi
-        need = _abi.load().lnw_ppo_sample_workspace_bytes(rows, batch)
-        if need <= 0:
-            raise _abi.LnwError(f"lnw_ppo_sample does not support rows={rows}, batch={batch}")
-        buf["ws"] = torch.empty(need, dtype=torch.uint8, device=device)
-    return buf
-
-
-def draw(priority, batch, seed, counter, status, row_base=0, advance=True, impl="hip", buf=None):
-    """The keyed draw over the flattened priorities: dict(index [B] int64 local
-    rows e * cap + k in draw order, key [B] float64). counter: int64 [1], the
-    slot of the draw, read where it lives and advanced by one unless advance is
-    False; status: int64 [1], receives the count of non-finite priorities (the
-    empty slots, unless the caller planted others). buf: draw_buffers to write."""
-    _check_impl(impl)
-    p = priority.reshape(-1)
-    N, B = p.shape[0], int(batch)
-    if not 1 <= B <= min(N, LNW_SAMPLE_MAX_BATCH):
-        raise ValueError(f"batch must be in 1 .. min(rows, {LNW_SAMPLE_MAX_BATCH})")
-    seed = int(seed) & (2 ** 64 - 1)
-    if buf is None:
-        buf = draw_buffers(N, B, p.device, impl)
-    if impl == "hip":
-        from . import _abi
-        L = _abi.load()
-        a = _abi.PpoSampleArgs()
-        a.rtg, a.rows, a.row_base, a.batch, a.seed = p.data_ptr(), N, int(row_base), B, seed
-        a.draw_dev, a.advance, a.n = counter.data_ptr(), int(bool(advance)), 1
-        a.index_out, a.key_out, a.status = buf["index"].data_ptr(), buf["key"].data_ptr(), status.data_ptr()
-        a.workspace, a.workspace_bytes = buf["ws"].data_ptr(), buf["ws"].numel()
-        _abi.check(L.lnw_ppo_sample(C.byref(a), _stream(p.device)))
-        return buf
-    from .ppolearn import sample_keys
-    h = p.detach().cpu().numpy()
-    key = sample_keys(h, seed, int(counter), int(row_base))
-    # ascending key, ties to the lower row (PPOLearner._sample_torch)
-    order = np.lexsort((np.arange(N), key))[:B]
-    buf["index"].copy_(torch.from_numpy(order.astype(np.int64)))
-    buf["key"].copy_(torch.from_numpy(key[order]))
-    status.fill_(int((~np.isfinite(h)).sum()))
-    if advance:
-        counter += 1
-    return buf
 
 
 def _regions(batch, n, D, reward_f64):
@@ -162,12 +103,11 @@ def pack(ring, global_row, src_rank=None, rank=0, row_base=0, impl="hip", xbuf=N
     other slot, in a slot whose row lies outside the ring, and in the padding.
     xbuf: the buffer to write, else a new one. index_out: int64 [B] to receive
     ring step * E + env per slot (-1 for a slot of zeros)."""
-    _check_impl(impl)
+    check_impl(impl)
     cap, E, n, D, f64 = ring_shape(ring)
     B = global_row.shape[0]
     dev = ring["state"].device
     if impl == "hip":
-        from . import _abi
         L = _abi.load()
         words = L.lnw_replay_pack_words(B, n, D, int(f64))
         if words <= 0:
@@ -184,7 +124,7 @@ def pack(ring, global_row, src_rank=None, rank=0, row_base=0, impl="hip", xbuf=N
         if index_out is not None:
             a.index_out = index_out.data_ptr()
         a.xbuf, a.xbuf_words = xbuf.data_ptr(), xbuf.numel()
-        _abi.check(L.lnw_replay_pack(C.byref(a), _stream(dev)))
+        _abi.check(L.lnw_replay_pack(C.byref(a), _abi.stream(dev)))
         return xbuf
     o_next, o_act, o_rew, o_done, words = _regions(B, n, D, f64)
     if xbuf is None:
@@ -221,21 +161,6 @@ def unpack(xbuf, batch, n, D, reward_f64):
                 action=xbuf[o_act:o_rew].view(B * n, 4), reward=rew, done=xbuf[o_done:o_done + B * n])
 
 
-def _check_batch(batch, filled, E):
-    B = int(batch)
-    if not 1 <= B <= min(int(filled) * E, LNW_SAMPLE_MAX_BATCH):
-        raise ValueError(f"batch must be in 1 .. min(filled * E, {LNW_SAMPLE_MAX_BATCH})")
-    return B
-
-
-def _buffers(cache, key, make):
-    if cache is None:
-        return make()
-    if key not in cache:
-        cache[key] = make()
-    return cache[key]
-
-
 def minibatch(ring, priority, batch, filled, seed, counter, status, row_base=0, advance=True, impl="hip",
               cache=None):
     """Draw, then pack with every slot owned: the dict QLearner.step() / grad()
@@ -244,9 +169,9 @@ def minibatch(ring, priority, batch, filled, seed, counter, status, row_base=0, 
     transitions; batch > filled * E raises ValueError before anything runs, so no
     empty slot is drawn. cache: a dict that keeps the buffers per batch size (the
     next call of that size overwrites them); None allocates new ones."""
-    _check_impl(impl)
+    check_impl(impl)
     cap, E, n, D, f64 = ring_shape(ring)
-    B = _check_batch(batch, filled, E)
+    B = check_batch(batch, int(filled) * E, "filled * E")
     dev = priority.device
 
     def make():
@@ -256,7 +181,7 @@ def minibatch(ring, priority, batch, filled, seed, counter, status, row_base=0, 
         buf["xbuf"] = torch.empty(pack_words(B, n, D, f64), dtype=torch.int32, device=dev)
         return buf
 
-    buf = _buffers(cache, ("local", B), make)
+    buf = cached(cache, ("local", B), make)
     draw(priority, B, seed, counter, status, row_base, advance, impl, buf)
     torch.add(buf["index"], int(row_base), out=buf["global_row"])
     pack(ring, buf["global_row"], None, 0, row_base, impl, buf["xbuf"], buf["ring_index"])
@@ -270,24 +195,17 @@ def minibatch_dist(ring, priority, batch, filled, seed, counter, status, row_bas
     """minibatch() over the union of the ranks' rings (QCollector.minibatch_dist
     has the contract): dict of unpack's row tensors, key and global_row. status
     receives the count over all ranks."""
-    _check_impl(impl)
+    check_impl(impl)
     cap, E, n, D, f64 = ring_shape(ring)
-    B = _check_batch(batch, filled, E)  # raises before any collective
+    B = check_batch(batch, int(filled) * E, "filled * E")  # raises before any collective
     dev = priority.device
-
-    def make():
-        buf = dict(draw=draw_buffers(E * cap, B, dev, impl), merge=ppodist.merge_buffers(B, dev))
-        buf["merge"]["status"] = status  # the global count replaces the local one
-        buf["xbuf"] = torch.empty(pack_words(B, n, D, f64), dtype=torch.int32, device=dev)
-        return buf
-
-    buf = _buffers(cache, ("dist", B), make)
+    buf = cached(cache, ("dist", B), lambda: dict(
+        draw=draw_buffers(E * cap, B, dev, impl), merge=ppodist.merge_buffers(B, dev),
+        xbuf=torch.empty(pack_words(B, n, D, f64), dtype=torch.int32, device=dev)))
     local = draw(priority, B, seed, counter, status, row_base, advance, impl, buf["draw"])
-    rank, _ = dist.rank_size(group)
-    lists = dist.all_gather(ppodist.message(local, row_base, status), group)
-    merged = ppodist.merge(lists, B, 1, impl, out=buf["merge"])
-    xbuf = pack(ring, merged["global_row"], merged["src_rank"], rank, row_base, impl, buf["xbuf"])
-    dist.all_reduce_sum_(xbuf, group)
+    merged, xbuf = ppodist.exchange(local, status, row_base, B, 1, impl, group, buf["merge"],
+                                    lambda m, rank: pack(ring, m["global_row"], m["src_rank"], rank, row_base, impl,
+                                                         buf["xbuf"]))
     out = unpack(xbuf, B, n, D, f64)
     out.update(key=merged["key"], global_row=merged["global_row"])
     return out

@@ -16,10 +16,12 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.distributions import Normal
 
+from . import _abi, layout
 from .batched import BatchedGame
+from .keyed import keyed_normal, keyed_uniform
+from .layout import ACTOR_NAMES, CONV_PARAMS, WINDOW, actor_slices, flat_size
 
 DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data")
-WINDOW = 49  # the 7x7 terrain window at the head of a Combatant observation
 
 
 class BatchedActor(nn.Module):
@@ -71,12 +73,7 @@ class BatchedActor(nn.Module):
         """Parameters in lnw_actor_features' order (csrc/lnw_actor.hip): conv1
         w, b; norm1 w, b, running mean, var; conv2 w, b; norm2 w, b, running
         mean, var; convhead w, b; layernorm w, b (578 + 2 n_in floats)."""
-        parts = [self.conv1.weight, self.conv1.bias, self.norm1.weight, self.norm1.bias,
-                 self.norm1.running_mean, self.norm1.running_var, self.conv2.weight,
-                 self.conv2.bias, self.norm2.weight, self.norm2.bias, self.norm2.running_mean,
-                 self.norm2.running_var, self.convhead.weight, self.convhead.bias,
-                 self.layernorm.weight, self.layernorm.bias]
-        return torch.cat([p.detach().reshape(-1).float() for p in parts]).contiguous()
+        return layout.pack(self, ACTOR_NAMES[:16])
 
     def packed_policy(self):
         """Every parameter lnw_policy_act reads (csrc/lnw_actor.hip), in its order:
@@ -119,7 +116,6 @@ class BatchedActor(nn.Module):
         for device tensors (lnw_actor_features), torch ops for host tensors."""
         B = obs.shape[0]
         if obs.is_cuda:
-            from . import _abi
             L = _abi.load()
             obs = obs.contiguous().float()
             n_in = self.layernorm.normalized_shape[0]
@@ -127,7 +123,7 @@ class BatchedActor(nn.Module):
             params = self.packed_features()
             _abi.check(L.lnw_actor_features(params.data_ptr(), obs.shape[1], obs.data_ptr(), B,
                                             0 if bn == "sample" else 1, out.data_ptr(),
-                                            torch.cuda.current_stream(obs.device).cuda_stream))
+                                            _abi.stream(obs.device)))
             return out
         z = obs[:, :WINDOW].reshape(B, 1, 7, 7)
         z = self.pool(F.relu(self._bn(self.norm1, self.conv1(z), bn)))
@@ -225,46 +221,10 @@ class BatchedCritic(nn.Module):
         return self.fc4(x)
 
 
-def keyed_normal(row0, rows, cols, seed, slot, device):
-    """Standard-normal draws [rows, cols] for global rows row0 .. row0+rows-1,
-    a pure function of (seed, slot, global row, column): Philox uniforms
-    (lnw_fill_uniform_f32, the bench's action generator) at absolute counter
-    slot * 2^40 + row * 2 * cols + k, then Box-Muller. A rank holding global
-    envs [lo, hi) draws exactly the values one rank holding all envs draws for
-    them, so a sharded rollout samples what an unsharded one does."""
-    u = keyed_uniform(row0, rows, cols, seed, slot, device)
-    r = torch.sqrt(-2.0 * torch.log1p(-u[:, :cols]))  # 1 - u in (0, 1]
-    return r * torch.cos((2.0 * np.pi) * u[:, cols:])
-
-
-def keyed_uniform(row0, rows, cols, seed, slot, device):
-    """The uniforms [rows, 2 cols] under keyed_normal's draws: row r holds the
-    Philox stream's values at slot * 2^40 + (row0 + r) * 2 * cols + k (radii for
-    k < cols, then angles). The fill starts at a multiple of 4 (one Philox block
-    holds four values); an offset that is none (row0 * 2 * cols odd pairs: the
-    parameter-noise rows, cols = the flat actor size) is filled from the block
-    below and cut."""
-    from . import _abi
-    L = _abi.load()
-    per = 2 * cols
-    off = (int(slot) << 40) + int(row0) * per
-    lead = off & 3
-    u = torch.empty(lead + rows * per, dtype=torch.float32, device=device)
-    _abi.check(L.lnw_fill_uniform_f32(u.data_ptr(), u.numel(), int(seed), off - lead,
-                                      torch.cuda.current_stream(device).cuda_stream))
-    return u[lead:].reshape(rows, per)
-
-
 # ---- parameter noise (ppo.py:452-482): flat and packed actor vectors -----------
-# The flat layout is the learner's (ppolearn.actor_slices, include/lnw.h), the
+# The flat layout is the learner's (layout.actor_slices, include/lnw.h), the
 # packed one what lnw_policy_act reads (BatchedActor.packed_policy()).
 NOISE_FREE = ("norm1", "norm2", "layernorm")  # name parts the reference leaves alone (ppo.py:470-473)
-
-
-def _flat_layout(n_in):
-    from .ppolearn import actor_slices, flat_size  # (ppolearn imports this module)
-    sl = actor_slices(n_in)
-    return sl, flat_size(sl)
 
 
 def flat_n_in(P):
@@ -280,8 +240,8 @@ def noise_mask(n_in, device=None):
     weight and bias of conv1, conv2, convhead, fc1, fc2, fc3 and the two heads; 0
     on norm1.*, norm2.* (running statistics included), layernorm.* and the logstd
     slot (which the reference noises, and nothing reads)."""
-    sl, P = _flat_layout(n_in)
-    m = torch.zeros(P, dtype=torch.float32)
+    sl = actor_slices(n_in)
+    m = torch.zeros(flat_size(sl), dtype=torch.float32)
     for name, (k, shp) in sl.items():
         if name != "logstd" and not any(s in name for s in NOISE_FREE):
             m[k:k + int(np.prod(shp))] = 1.0
@@ -293,11 +253,12 @@ def unpack_policy(packed, n_in):
     flat vectors [..., P], bit for bit (hi + mid + lo of a weight's three
     bfloat16 terms is exact in float32). The logstd slot, which the packed set
     does not hold, is 0."""
-    sl, P = _flat_layout(n_in)
+    sl = actor_slices(n_in)
+    P = flat_size(sl)
     x = packed.reshape(-1, packed.shape[-1])
     M = x.shape[0]
     out = torch.zeros((M, P), dtype=torch.float32, device=x.device)
-    n_par = 578 + 2 * n_in
+    n_par = CONV_PARAMS + 2 * n_in
     out[:, :n_par] = x[:, :n_par]
     o = (n_par + 3) & ~3
     for name, cnt in (("fc1.bias", 64), ("fc2.bias", 64), ("fc3.bias", 32)):
@@ -537,8 +498,7 @@ class Rollout:
                  side="blue", warmup=None):
         if observe not in ("fresh", "step"):
             raise ValueError("observe must be 'fresh' or 'step'")
-        if impl not in ("hip", "torch"):
-            raise ValueError("impl must be 'hip' or 'torch'")
+        _abi.check_impl(impl)
         if side not in ("blue", "red"):
             raise ValueError("side must be 'blue' or 'red'")
         if red is None:  # blue trains against the scripted profiles, red against the blue actor
@@ -656,10 +616,10 @@ class Rollout:
         """The flat actor vector(s) of this run on the game's device: the
         explicit member vectors [M, P], else `theta` [P] as it stands now, else
         the module's parameters packed into the flat layout."""
-        from .ppolearn import pack
         dev = self.g.device
         actor = self._learning()[0]
-        sl, P = _flat_layout(actor.layernorm.normalized_shape[0])
+        sl = actor_slices(actor.layernorm.normalized_shape[0])
+        P = flat_size(sl)
         if self.member_thetas is not None:
             src = self.member_thetas.to(device=dev, dtype=torch.float32).contiguous()
         elif self.theta is not None:
@@ -667,7 +627,7 @@ class Rollout:
             if src.dtype != torch.float32 or src.device != dev or not src.is_contiguous() or src.dim() != 1:
                 raise ValueError("theta must be a contiguous float32 vector on the game's device")
         else:
-            src = pack(actor, sl).to(dev)
+            src = layout.pack(actor, sl).to(dev)
         if src.shape[-1] != P:
             raise ValueError(f"the flat actor vector holds {P} floats, not {src.shape[-1]}")
         return src
@@ -686,19 +646,11 @@ class Rollout:
             std, clip = self.param_noise.tolist() if self.param_noise is not None else (0.0, 0.0)
             src = perturbed_theta(src, g.env_id_base // G, M, std, clip, seed, int(self._call.item()), self.T)
         actor = self._learning()[0]
-        sl, _ = _flat_layout(actor.layernorm.normalized_shape[0])
-        actors = []
-        for k in range(M):
-            net = copy.deepcopy(actor)
-            sd = net.state_dict()  # (tensors sharing the copy's storage)
-            for name, (o, shp) in sl.items():
-                sd[name].copy_(src[k, o:o + int(np.prod(shp))].reshape(shp))
-            actors.append(net)
-        return G, actors
+        sl = actor_slices(actor.layernorm.normalized_shape[0])
+        return G, [layout.unpack_(copy.deepcopy(actor), src[k], sl) for k in range(M)]
 
     def _run_hip(self, forced_actions, on_step):
         import ctypes as C
-        from . import _abi
         from ._abi import F_ALIVE, PolicyArgs, RolloutPostArgs
         L = _abi.load()
         g = self.g
@@ -717,7 +669,7 @@ class Rollout:
         # rollout's frozen blue actor (its launch writes action rows only)
         other_rows = red_side or (self.red != "script" and self.red_actor is not None)
         seed = int(self.keyed_seed if self.keyed_seed is not None else self.seed) & (2**64 - 1)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _abi.stream(dev)
         pop = None
         if self.G is not None or self.theta is not None:
             # the members' packed sets [M, floats] from the flat vector(s), on the device
