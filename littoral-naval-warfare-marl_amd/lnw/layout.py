@@ -3,7 +3,7 @@ actor's and the critic's flat layouts (include/lnw.h; PPOLearner's theta_actor
 and theta_critic, Rollout's `theta`), the Q-net's packed() layout (lnw_qnet_act,
 QLearner's theta), and the copy of a module's parameters and running statistics
 into such a vector and back. No network code: the forward passes that read
-these layouts are lnw/rollout.py, lnw/ppolearn.py and lnw/qlearn.py.
+these layouts are lnw/nets.py's.
 """
 import numpy as np
 import torch

@@ -12,57 +12,22 @@ the keyed minibatch draw behind PPOLearner.minibatch: lnw/keyed.py, with its
 host restatement sample_keys) and csrc/lnw_ppodist.hip (the merge and the row
 exchange behind PPOLearner.minibatch_dist, which trains on rollouts sharded
 over ranks: lnw/ppodist.py). The flat layouts are lnw/layout.py's
-(actor_slices, critic_slices, pack). learn()'s outer schedule
+(actor_slices, critic_slices, pack), the torch arm's forwards lnw/nets.py's
+(actor_forward, critic_forward). learn()'s outer schedule
 (noise ratio, lr halving on victories, epoch count) stays with the caller;
 parameter noise is the rollout's (lnw.rollout.Rollout(param_noise=..., theta=
 learner.theta_actor) acts from this learner's flat vector).
 """
 import ctypes as C
-from functools import partial
 
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
-from torch.distributions import Normal
 
 from . import _abi, keyed, layout
 from .keyed import _p_log, _philox10, sample_keys  # noqa: F401  (the draw's host restatement lives there)
 from .layout import (ACTOR_NAMES, CONV_PARAMS, CRITIC_NAMES, RUNNING, WINDOW, actor_slices,  # noqa: F401
                      critic_slices, flat_size, pack)
-
-
-def actor_forward(theta, obs, actions, sl):
-    """MLP.get_dist (network.py:117-152) of every row with the row's own
-    BatchNorm statistics, from a flat parameter vector (differentiable in
-    theta): log-probabilities [B, 4], entropies [B, 4], and the rows'
-    statistics [B, 26] (13 channel means, then their unbiased variances)."""
-    seg = partial(layout.seg, theta, sl)
-    B = obs.shape[0]
-    z = obs[:, :WINDOW].reshape(B, 1, 7, 7)
-    z1 = F.conv2d(z, seg("conv1.weight"), seg("conv1.bias"), padding=1)
-    z = F.max_pool2d(F.relu(F.instance_norm(z1, weight=seg("norm1.weight"), bias=seg("norm1.bias"), eps=1e-5)), 2, 2)
-    z2 = F.conv2d(z, seg("conv2.weight"), seg("conv2.bias"), padding=1)
-    z = F.max_pool2d(F.relu(F.instance_norm(z2, weight=seg("norm2.weight"), bias=seg("norm2.bias"), eps=1e-5)), 2, 2)
-    with torch.no_grad():
-        stats = torch.cat([z1.mean((2, 3)), z2.mean((2, 3)), z1.var((2, 3), unbiased=True),
-                           z2.var((2, 3), unbiased=True)], 1)
-    x = torch.cat((F.linear(torch.flatten(z, 1), seg("convhead.weight"), seg("convhead.bias")), obs[:, WINDOW:]), 1)
-    x = F.layer_norm(x, (x.shape[1],), seg("layernorm.weight"), seg("layernorm.bias"), 1e-5)
-    x = torch.tanh(F.linear(x, seg("fc1.weight"), seg("fc1.bias")))
-    x = torch.tanh(F.linear(x, seg("fc2.weight"), seg("fc2.bias")))
-    x = torch.tanh(F.linear(x, seg("fc3.weight"), seg("fc3.bias")))
-    dist = Normal(torch.tanh(F.linear(x, seg("normal_head.weight"))),
-                  torch.exp(F.linear(x, seg("log_std_head.weight"))), validate_args=False)
-    return dist.log_prob(actions), dist.entropy(), stats
-
-
-def critic_forward(theta, gs, sl):
-    """Value.forward (network.py:168-175) from a flat parameter vector: [B]."""
-    seg = partial(layout.seg, theta, sl)
-    x = torch.tanh(F.linear(gs, seg("fc1.weight"), seg("fc1.bias")))
-    x = torch.tanh(F.linear(x, seg("fc2.weight"), seg("fc2.bias")))
-    x = torch.tanh(F.linear(x, seg("fc3.weight"), seg("fc3.bias")))
-    return F.linear(x, seg("fc4.weight"), seg("fc4.bias"))[:, 0]
+from .nets import actor_forward, critic_forward
 
 
 def gae_rows(rtg, values, gamma, lambda_, block=512):

@@ -1,44 +1,35 @@
-"""On-device DDQN acting around the batched step (DISCRETE mode): the
-reference's Q-network evaluated for every (env, ship) at once, epsilon-greedy
-and untrained-red random actions from keyed Philox draws, and a transition
-collector that fills a device replay ring. Observations never leave the GPU.
+"""On-device DDQN around the batched step (DISCRETE mode), acting with the
+reference's Q-network (BatchedQNet and q_forward, lnw/nets.py): the epsilon
+schedule, untrained red's random actions from keyed Philox draws, and a
+transition collector that fills a device replay ring. Observations never leave
+the GPU.
 
-Reference: network.py:246-305 (DMLP), ddqn.py:149-151 (get_epsilon),
-ddqn.py:286-387 (acting), ddqn.py:153-247 (optimize(): QLearner, the TD loss,
-its gradient and the clamped Adam step as HIP kernels, csrc/lnw_qlearn.hip).
+Reference: ddqn.py:149-151 (get_epsilon), ddqn.py:286-387 (acting),
+ddqn.py:153-247 (optimize(): QLearner, the TD loss, its gradient and the
+clamped Adam step as HIP kernels, csrc/lnw_qlearn.hip).
 QCollector.minibatch / minibatch_dist draw the replay minibatch on the device,
 without replacement, uniformly or by priorities kept beside the ring
 (lnw/replay.py, csrc/lnw_replay.hip).
 """
 import ctypes as C
 import math
-from functools import partial
 
-import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _abi, layout
+from . import _abi
 from .batched import BatchedGame
-from .keyed import keyed_uniform4
+from .keyed import keyed_uniform4  # noqa: F401
 from .layout import CONV_PARAMS, N_ATTACK, N_MOVE, N_RADAR, PACKED_NAMES, WINDOW, packed_slices  # noqa: F401
+from .nets import HEADS, N_Q, BatchedQNet, q_forward, random_rows  # noqa: F401
 
-N_Q = N_RADAR + N_ATTACK + N_MOVE             # 57, in radar, attack, movement order
-HEADS = ((0, N_RADAR), (N_RADAR, N_RADAR + N_ATTACK), (N_RADAR + N_ATTACK, N_Q))
+_flat_forward = q_forward  # (its name before lnw/nets.py)
 
 
 def epsilon(t, start, end, decay):
     """ddqn.py:149-151 `get_epsilon`: end + (start - end) * exp(-t / decay)."""
     return end + (start - end) * math.exp(-1. * t / decay)
-
-
-def random_rows(u):
-    """The random rows [B, 3] of ddqn.py:300 from uniforms u [B, 4] (u0 decides
-    whether a row explores, u0 < eps): [(int)(u1*2), (int)(u2*5), (int)(u3*50)],
-    float32 multiply then truncate."""
-    return torch.stack([(u[:, 1] * 2.0).to(torch.int32), (u[:, 2] * 5.0).to(torch.int32),
-                        (u[:, 3] * 50.0).to(torch.int32)], 1)
 
 
 def red_random_rows(u, t, red_aggression, tl_cnt):
@@ -50,187 +41,6 @@ def red_random_rows(u, t, red_aggression, tl_cnt):
     fire = (u[:, 1] < torch.tensor(red_aggression, dtype=torch.float32, device=u.device)) & (tl_cnt > 0)
     msl = torch.where(fire, 1 + (u[:, 2] * 4.0).to(torch.int32), torch.zeros_like(rad))
     return torch.stack([rad, msl, (u[:, 3] * 50.0).to(torch.int32)], 1)
-
-
-class BatchedQNet(nn.Module):
-    """network.py:246-305 `DMLP` for a [B, D] batch of observations.
-
-    Same submodules, parameter names and initialisation as the reference, so a
-    reference `state_dict` loads as is (`load_reference`). The DDQN loop calls
-    `target_net` one state at a time and never puts it in eval()
-    (ddqn.py:303), i.e. with BatchNorm statistics of that single sample:
-    `bn="sample"` reproduces that for every row, `bn="running"` is the eval-mode
-    network, `bn="batch"` normalises with the statistics of the whole batch as
-    optimize()'s train-mode calls do (ddqn.py:175, 185; torch ops only, and the
-    mode to differentiate through). Running statistics are not updated.
-    """
-
-    def __init__(self, n_inputs):
-        super().__init__()
-        self.conv1 = nn.Conv2d(1, 5, 3, 1, padding=1)
-        self.norm1 = nn.BatchNorm2d(5)
-        self.pool = nn.MaxPool2d(2, 2)
-        self.conv2 = nn.Conv2d(5, 8, 3, 1, padding=1)
-        self.norm2 = nn.BatchNorm2d(8)
-        self.pool2 = nn.MaxPool2d(2, 2)
-        self.convhead = nn.Linear(8, 12, bias=True)
-        n_in = n_inputs - WINDOW + 12
-        self.movement = nn.Linear(n_in, N_MOVE, bias=True)
-        self.attack = nn.Linear(n_in, N_ATTACK, bias=True)
-        self.radar = nn.Linear(n_in, N_RADAR, bias=True)
-        for m in (self.convhead, self.movement, self.attack, self.radar):
-            nn.init.xavier_uniform_(m.weight)
-        self.obs_dim, self.n_in = int(n_inputs), int(n_in)
-
-    @classmethod
-    def for_obs(cls, obs_dim):
-        """The reference sizing: DMLP(n_inputs = observation row length)."""
-        return cls(obs_dim)
-
-    def load_reference(self, state_dict):
-        """Load a reference DMLP state_dict (tensors or arrays)."""
-        own = self.state_dict()
-        self.load_state_dict({k: torch.as_tensor(np.asarray(v)).reshape(own[k].shape)
-                              for k, v in state_dict.items()})
-        return self
-
-    def packed(self):
-        """Every parameter lnw_qnet_act reads (csrc/lnw_qnet.hip), in its order:
-        the conv head in lnw_actor_features' order (578 floats), then W [57][n_in]
-        with the rows in radar, attack, movement order, then b [57]."""
-        return layout.pack(self, packed_slices(self.n_in))
-
-    @torch.no_grad()
-    def unpack_(self, flat):
-        """The inverse of packed(): load a flat vector in its layout into the
-        parameters and running statistics, in place."""
-        sl = packed_slices(self.n_in)
-        if flat.numel() != layout.flat_size(sl):
-            raise ValueError("flat vector length does not match packed()")
-        return layout.unpack_(self, flat, sl)
-
-    @staticmethod
-    def _bn(m, z, bn):
-        if bn == "sample":
-            return F.instance_norm(z, weight=m.weight, bias=m.bias, eps=m.eps)
-        if bn == "batch":
-            return F.batch_norm(z, None, None, m.weight, m.bias, True, 0.0, m.eps)
-        if bn == "running":
-            return F.batch_norm(z, m.running_mean, m.running_var, m.weight, m.bias, False, 0.0, m.eps)
-        raise ValueError("bn must be 'sample', 'running' or 'batch'")
-
-    def q_torch(self, obs, bn="sample"):
-        """DMLP.forward as torch ops (host or device): [B, 57] = [radar,
-        attack, movement] after the ReLU."""
-        B = obs.shape[0]
-        z = obs[:, :WINDOW].reshape(B, 1, 7, 7)
-        z = self.pool(F.relu(self._bn(self.norm1, self.conv1(z), bn)))
-        z = self.pool2(F.relu(self._bn(self.norm2, self.conv2(z), bn)))
-        x = torch.cat((self.convhead(torch.flatten(z, 1)), obs[:, WINDOW:]), 1)
-        return torch.cat((F.relu(self.radar(x)), F.relu(self.attack(x)), F.relu(self.movement(x))), 1)
-
-    def q(self, obs, bn="sample"):
-        """The ReLU'd Q-values [B, 57] of obs [B, D]: the HIP kernel
-        (lnw_qnet_act's q_out) for device tensors, torch ops for host tensors
-        and for bn="batch"."""
-        if not obs.is_cuda or bn == "batch":
-            return self.q_torch(obs, bn)
-        if bn not in ("sample", "running"):
-            raise ValueError("bn must be 'sample', 'running' or 'batch'")
-        B = obs.shape[0]
-        alive = torch.ones(B, dtype=torch.uint8, device=obs.device)
-        return self._launch(obs.reshape(B, 1, -1), alive, 0, 1, bn=bn, want_q=True, want_act=False)["q"]
-
-    def _launch(self, obs, alive, own0, A, eps=0.0, eps_env=None, live=None, seed=0, slot=0,
-                row_base=0, bn="sample", full=None, act_out=None, act_env_stride=0,
-                obs_in_env_stride=0, want_q=False, want_act=True, want_explored=False, params=None):
-        """One lnw_qnet_act launch (EPS_GREEDY) for this side's rows: obs a
-        tensor [E, n, D], or (device pointer, (E, n, D), device) for rows in
-        caller memory (env e at pointer + e * obs_in_env_stride floats); alive:
-        [A][E] uint8 tensor or a device pointer."""
-        L = _abi.load()
-        if torch.is_tensor(obs):
-            obs = obs.contiguous().float()
-            obs_ptr, (E, n, D), dev = obs.data_ptr(), obs.shape, obs.device
-        else:
-            obs_ptr, (E, n, D), dev = obs
-        a = _abi.QnetArgs()
-        a.obs, a.E, a.n, a.D, a.own0, a.A = obs_ptr, E, n, D, own0, A
-        a.obs_in_env_stride = int(obs_in_env_stride)
-        params = self.packed() if params is None else params
-        a.params, a.bn_running, a.mode = params.data_ptr(), int(bn == "running"), _abi.LNW_QNET_EPS_GREEDY
-        if eps_env is not None:
-            eps_env = eps_env.to(device=dev, dtype=torch.float32).contiguous()
-            a.eps_env = eps_env.data_ptr()
-        a.eps = float(eps)
-        a.seed, a.slot, a.row_base = int(seed) & (2**64 - 1), int(slot), int(row_base)
-        a.alive = alive.data_ptr() if torch.is_tensor(alive) else alive
-        if live is not None:
-            live = live.to(device=dev).contiguous()
-            a.live = live.data_ptr()
-        out = {}
-        if want_act and full is None and act_out is None:
-            out["actions"] = torch.empty((E, n, 4), dtype=torch.int32, device=dev)
-            a.act_out, a.act_env_stride = out["actions"].data_ptr(), n * 4
-        if full is not None:
-            a.full = full.data_ptr() if torch.is_tensor(full) else full
-        if act_out is not None:
-            a.act_out, a.act_env_stride = act_out, int(act_env_stride)
-        if want_q:
-            out["q"] = torch.empty((E * n, N_Q), dtype=torch.float32, device=dev)
-            a.q_out = out["q"].data_ptr()
-        if want_explored:
-            out["explored"] = torch.empty((E * n,), dtype=torch.uint8, device=dev)
-            a.explored = out["explored"].data_ptr()
-        _abi.check(L.lnw_qnet_act(C.byref(a), _abi.stream(dev)))
-        return out
-
-    @torch.no_grad()
-    def act(self, obs, eps=0.0, alive=None, live=None, seed=0, slot=0, row_base=0, bn="sample",
-            impl="hip", want_q=False):
-        """Epsilon-greedy actions (ddqn.py:294-312) for one side's rows obs
-        [E, n, D] on the device: dict(actions [E, n, 4] int32 (column 3 zero),
-        explored [E, n] bool, q [E*n, 57] if want_q). eps: a float, or a per-env
-        tensor [E]. alive: [E, n] (rows of sunk ships act 0, 0, 0); live: [E].
-        impl="hip": one lnw_qnet_act launch. impl="torch": the same as torch ops
-        with the same keyed draws (keyed_uniform4) — the restatement the kernel's
-        random branch is tested against; its greedy rows come from q_torch, so
-        they may differ from the kernel's where two Q-values are within
-        rounding."""
-        E, n, D = obs.shape
-        dev = obs.device
-        eps_env = eps if torch.is_tensor(eps) else None
-        al = torch.ones((E, n), dtype=torch.bool, device=dev) if alive is None else alive.to(dev).bool()
-        if impl == "hip":
-            o = self._launch(obs, al.t().contiguous().to(torch.uint8), 0, n, eps=0.0 if eps_env is not None else eps,
-                             eps_env=eps_env, live=None if live is None else live.to(torch.uint8),
-                             seed=seed, slot=slot, row_base=row_base, bn=bn, want_q=want_q, want_explored=True)
-            o["explored"] = o["explored"].bool().reshape(E, n)
-            return o
-        _abi.check_impl(impl)
-        q = self.q_torch(obs.reshape(E * n, D).float(), bn)
-        greedy = torch.stack([q[:, lo:hi].argmax(1) for lo, hi in HEADS], 1).to(torch.int32)
-        u = keyed_uniform4(row_base, E * n, seed, slot, dev)
-        e = (eps_env.to(dev).float()[:, None].expand(E, n).reshape(-1) if eps_env is not None
-             else torch.tensor(float(eps), dtype=torch.float32, device=dev))
-        explore = u[:, 0] < e
-        rows = torch.where(explore[:, None], random_rows(u), greedy)
-        keep = al.reshape(-1) if live is None else (al & live.to(dev).bool()[:, None]).reshape(-1)
-        act = torch.zeros((E * n, 4), dtype=torch.int32, device=dev)
-        act[:, :3] = torch.where(keep[:, None], rows, torch.zeros_like(rows))
-        out = dict(actions=act.reshape(E, n, 4), explored=(explore & keep).reshape(E, n))
-        if want_q:
-            out["q"] = q
-        return out
-
-    @torch.no_grad()
-    def td_target(self, next_obs, reward, done, gamma, bn="batch"):
-        """ddqn.py:175-193: per-head max of this (target) network on next_obs
-        [B, D], then gamma * max * done + reward -> [B, 3] float32 (done is 1
-        while the episode runs, as lnw_step returns it)."""
-        q = self.q(next_obs, bn)
-        nxt = torch.stack([q[:, lo:hi].max(1).values for lo, hi in HEADS], 1)
-        return (gamma * nxt * done.to(nxt.dtype)[:, None] + reward.to(nxt.dtype)[:, None]).float()
 
 
 def red_random_act(game, full, t, seed, slot, live=None, act_out=None, act_env_stride=0, explored=None):
@@ -476,31 +286,6 @@ class QCollector:
                                      bool(advance), group, self.impl, self._replay_buf)
 
 
-def _flat_forward(theta, obs, bn, sl):
-    """DMLP.forward from a flat parameter vector (differentiable in theta):
-    q [B, 57] after the ReLU, and the batch mean / biased variance of the 13
-    BatchNorm channels [2, 13]. bn: "batch" or "running" (the running slots are
-    constants then)."""
-    seg = partial(layout.seg, theta, sl)
-    B = obs.shape[0]
-    stats = []
-
-    def norm(z, pre):
-        mean, var = z.mean((0, 2, 3)), z.var((0, 2, 3), unbiased=False)
-        stats.append((mean.detach(), var.detach()))
-        if bn == "batch":
-            return F.batch_norm(z, None, None, seg(pre + ".weight"), seg(pre + ".bias"), True, 0.0, 1e-5)
-        return F.batch_norm(z, seg(pre + ".running_mean").detach(), seg(pre + ".running_var").detach(),
-                            seg(pre + ".weight"), seg(pre + ".bias"), False, 0.0, 1e-5)
-
-    z = obs[:, :WINDOW].reshape(B, 1, 7, 7)
-    z = F.max_pool2d(F.relu(norm(F.conv2d(z, seg("conv1.weight"), seg("conv1.bias"), padding=1), "norm1")), 2, 2)
-    z = F.max_pool2d(F.relu(norm(F.conv2d(z, seg("conv2.weight"), seg("conv2.bias"), padding=1), "norm2")), 2, 2)
-    x = torch.cat((F.linear(torch.flatten(z, 1), seg("convhead.weight"), seg("convhead.bias")), obs[:, WINDOW:]), 1)
-    q = torch.cat([F.relu(F.linear(x, seg(h + ".weight"), seg(h + ".bias"))) for h in ("radar", "attack", "movement")], 1)
-    st = torch.stack([torch.cat([stats[0][0], stats[1][0]]), torch.cat([stats[0][1], stats[1][1]])])
-    return q, st
-
 
 class QLearner:
     """The learner half of the DDQN loop: ddqn.py:153-247 `optimize()` for one
@@ -627,12 +412,12 @@ class QLearner:
         B = r["state"].shape[0]
         sl = self.slices
         with torch.no_grad():
-            qt, st_t = _flat_forward(self.theta_target, r["next_state"], "batch", sl)
+            qt, st_t = q_forward(self.theta_target, r["next_state"], "batch", sl)
             nxt = torch.stack([qt[:, lo:hi].max(1).values for lo, hi in HEADS], 1)
             t = (self.gamma * nxt) * r["done"][:, None]
             y = (t + r["reward"][:, None]).float()  # (float64 rewards: the sum in float64, then float32)
         th = self.theta.detach().clone().requires_grad_(True)
-        q, st_p = _flat_forward(th, r["state"], self.policy_bn, sl)
+        q, st_p = q_forward(th, r["state"], self.policy_bn, sl)
         act = r["action"].long()
         qs = torch.stack([q[:, lo:hi].gather(1, act[:, h:h + 1].clamp(0, hi - lo - 1))[:, 0]
                           for h, (lo, hi) in enumerate(HEADS)], 1)

@@ -1,10 +1,10 @@
 """On-device MAPPO rollout pieces around the batched step (SURVEY.md §8(f) rows
-1-3): the reference's actor / critic evaluated for every (env, ship) at once,
-rollout storage as [E, T, ...] device tensors, the reference's reward-to-go and
-GAE as batched tensor ops, and the scripted red action profiles as a device
-table. Observations never leave the GPU.
+1-3): the reference's actor / critic (lnw/nets.py) acting for every (env, ship)
+at once, rollout storage as [E, T, ...] device tensors, the reference's
+reward-to-go and GAE as batched tensor ops, and the scripted red action
+profiles as a device table. Observations never leave the GPU.
 
-Reference: ppo.py:421-671 (rollout), network.py:38-172 (MLP, Value),
+Reference: ppo.py:421-671 (rollout), ppo.py:452-482 (parameter noise),
 ppo.py:645-659 (reward-to-go), ppo.py:695-714 (gae), game.py:173-182 and
 536-542 (red_steps*.csv profiles).
 """
@@ -12,270 +12,15 @@ import os
 
 import numpy as np
 import torch
-import torch.nn as nn
-import torch.nn.functional as F
-from torch.distributions import Normal
 
 from . import _abi, layout
 from .batched import BatchedGame
 from .keyed import keyed_normal, keyed_uniform
-from .layout import ACTOR_NAMES, CONV_PARAMS, WINDOW, actor_slices, flat_size
+from .layout import ACTOR_NAMES, CONV_PARAMS, WINDOW, actor_slices, flat_size  # noqa: F401
+from .nets import (NOISE_FREE, BatchedActor, BatchedCritic, flat_n_in, noise_mask,  # noqa: F401
+                   unpack_policy)
 
 DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data")
-
-
-class BatchedActor(nn.Module):
-    """network.py:38-152 `MLP` for a [B, D] batch of observations.
-
-    Same submodules, parameter names and initialisation as the reference, so a
-    reference `state_dict` loads as is (`load_reference`). The reference is a
-    batch-1 network: it flattens the conv head over the batch and concatenates
-    along dim 0 (network.py:83), and the PPO rollout calls it one state at a time
-    with BatchNorm in training mode (ppo.py:504-512), i.e. with statistics of that
-    single sample. `bn="sample"` reproduces exactly that for every row (instance
-    statistics with the BatchNorm affine parameters); `bn="running"` is the
-    eval-mode network (running statistics). Running statistics are not updated.
-    """
-
-    def __init__(self, n_inputs, n_outputs):
-        super().__init__()
-        self.conv1 = nn.Conv2d(1, 5, 3, 1, padding=1)
-        self.norm1 = nn.BatchNorm2d(5)
-        self.pool = nn.MaxPool2d(2, 2)
-        self.conv2 = nn.Conv2d(5, 8, 3, 1, padding=1)
-        self.norm2 = nn.BatchNorm2d(8)
-        self.pool2 = nn.MaxPool2d(2, 2)
-        self.convhead = nn.Linear(8, 12, bias=True)
-        self.layernorm = nn.LayerNorm(n_inputs)
-        self.fc1 = nn.Linear(n_inputs, 64, bias=True)
-        self.fc2 = nn.Linear(64, 64, bias=True)
-        self.fc3 = nn.Linear(64, 32, bias=True)
-        self.normal_head = nn.Linear(32, n_outputs, bias=False)
-        self.log_std_head = nn.Linear(32, n_outputs, bias=False)
-        for m in (self.fc1, self.fc2, self.fc3, self.normal_head, self.log_std_head):
-            nn.init.xavier_uniform_(m.weight)
-        self.logstd = nn.Parameter(torch.zeros(()))  # present in the reference, unused there too
-
-    @classmethod
-    def for_obs(cls, obs_dim, n_outputs=4):
-        """The reference sizing: n_inputs = obs_dim - 7*7 + 12 (ppo.py:78, 446)."""
-        return cls(obs_dim - WINDOW + 12, n_outputs)
-
-    def load_reference(self, state_dict):
-        """Load a reference MLP state_dict (tensors or arrays)."""
-        sd = {k: torch.as_tensor(np.asarray(v)) for k, v in state_dict.items()}
-        if "logstd" not in sd:
-            sd["logstd"] = torch.zeros(())
-        self.load_state_dict({k: v.reshape(self.state_dict()[k].shape) for k, v in sd.items()})
-        return self
-
-    def packed_features(self):
-        """Parameters in lnw_actor_features' order (csrc/lnw_actor.hip): conv1
-        w, b; norm1 w, b, running mean, var; conv2 w, b; norm2 w, b, running
-        mean, var; convhead w, b; layernorm w, b (578 + 2 n_in floats)."""
-        return layout.pack(self, ACTOR_NAMES[:16])
-
-    def packed_policy(self):
-        """Every parameter lnw_policy_act reads (csrc/lnw_actor.hip), in its order:
-        packed_features() zero-padded to a multiple of 4 floats; the biases b1
-        [64], b2 [64], b3 [32]; then the MFMA A-operand fragments of fc1 (n_in
-        zero-padded to 32 columns, 64 when n_in > 32), fc2, fc3 and the heads
-        (normal_head rows 0-3, log_std_head rows 4-7, zero rows to 16) for
-        v_mfma_f32_16x16x32_bf16 with each weight split exactly into three
-        bfloat16 terms (w = hi + mid + lo, round-to-nearest each): per layer three
-        planes (hi, mid, lo) of bf16x8 [n-tile][k-pair p][lane], element j =
-        W[16 nt + lane % 16][32 p + 16 (j // 4) + 4 (lane // 16) + j % 4] (the k
-        order the kernel's chained layers sum in), stored as raw bits, two per
-        float."""
-        n_in = self.layernorm.normalized_shape[0]
-        dev = self.fc1.weight.device
-
-        def frags(w, k_pad, n_pad):
-            wp = torch.zeros((n_pad, k_pad), dtype=torch.float32, device=dev)
-            wp[:w.shape[0], :w.shape[1]] = w.detach().float()
-            nt, qp = n_pad // 16, k_pad // 32
-            # [nt][m][p][half][g][v] -> [nt][p][lane = 16 g + m][j = 4 half + v]
-            x = wp.reshape(nt, 16, qp, 2, 4, 4).permute(0, 2, 4, 1, 3, 5).reshape(nt, qp, 64, 8)
-            hi = x.to(torch.bfloat16)
-            r = x - hi.float()
-            mid = r.to(torch.bfloat16)
-            lo = (r - mid.float()).to(torch.bfloat16)
-            return torch.stack([hi, mid, lo]).contiguous().reshape(-1).view(torch.float32)
-
-        conv = self.packed_features()
-        conv = torch.cat([conv, torch.zeros((-conv.numel()) % 4, device=dev)])
-        k1 = 32 if n_in <= 32 else 64
-        heads = torch.cat([self.normal_head.weight, self.log_std_head.weight], 0)
-        parts = [conv, self.fc1.bias, self.fc2.bias, self.fc3.bias,
-                 frags(self.fc1.weight, k1, 64), frags(self.fc2.weight, 64, 64),
-                 frags(self.fc3.weight, 64, 32), frags(heads, 32, 16)]
-        return torch.cat([p.detach().reshape(-1).float() for p in parts]).contiguous()
-
-    def features(self, obs, bn="sample"):
-        """network.py:70-85 up to the LayerNorm -> [B, n_in]: the HIP kernel
-        for device tensors (lnw_actor_features), torch ops for host tensors."""
-        B = obs.shape[0]
-        if obs.is_cuda:
-            L = _abi.load()
-            obs = obs.contiguous().float()
-            n_in = self.layernorm.normalized_shape[0]
-            out = torch.empty((B, n_in), dtype=torch.float32, device=obs.device)
-            params = self.packed_features()
-            _abi.check(L.lnw_actor_features(params.data_ptr(), obs.shape[1], obs.data_ptr(), B,
-                                            0 if bn == "sample" else 1, out.data_ptr(),
-                                            _abi.stream(obs.device)))
-            return out
-        z = obs[:, :WINDOW].reshape(B, 1, 7, 7)
-        z = self.pool(F.relu(self._bn(self.norm1, self.conv1(z), bn)))
-        z = self.pool2(F.relu(self._bn(self.norm2, self.conv2(z), bn)))
-        z = self.convhead(torch.flatten(z, 1))
-        return self.layernorm(torch.cat((z, obs[:, WINDOW:]), 1))
-
-    @staticmethod
-    def _bn(m, z, bn):
-        if bn == "sample":
-            return F.instance_norm(z, weight=m.weight, bias=m.bias, eps=m.eps)
-        return F.batch_norm(z, m.running_mean, m.running_var, m.weight, m.bias, False, 0.0, m.eps)
-
-    def heads(self, obs, bn="sample"):
-        """(normal mean, normal std) for every row of obs [B, D]."""
-        x = self.features(obs, bn)
-        x = torch.tanh(self.fc1(x))
-        x = torch.tanh(self.fc2(x))
-        x = torch.tanh(self.fc3(x))
-        return torch.tanh(self.normal_head(x)), torch.exp(self.log_std_head(x))
-
-    def forward(self, obs, noise=None, bn="sample", generator=None, eps=None, noise_eps=None):
-        """network.py:70-115 for every row: sample N(mean, std), add N(0, noise)
-        exploration noise, clamp to [0, 1], log-probabilities of the clamped
-        actions. Returns (actions, log_probs, ok) where ok marks rows without
-        NaN heads (the reference returns (None, None) for those). `eps` /
-        `noise_eps`: given standard-normal draws [B, n_outputs] instead of
-        drawing from `generator` (keyed_normal: shard-invariant rollouts)."""
-        mean, std = self.heads(obs, bn)
-        ok = ~(torch.isnan(mean).any(1) | torch.isnan(std).any(1))
-        mean_s = torch.where(ok[:, None], mean, torch.zeros_like(mean))
-        std_s = torch.where(ok[:, None], std, torch.ones_like(std))
-        dist = Normal(mean_s, std_s, validate_args=False)  # no host sync (graph capture)
-        if eps is None:
-            eps = torch.randn(mean.shape, generator=generator, device=mean.device, dtype=mean.dtype)
-        actions = mean_s + std_s * eps
-        if noise is not None:
-            if noise_eps is None:
-                noise_eps = torch.randn(mean.shape, generator=generator, device=mean.device,
-                                        dtype=mean.dtype)
-            actions = actions + noise * noise_eps
-        actions = torch.clamp(actions, 0, 1)
-        return actions, dist.log_prob(actions), ok
-
-    def get_dist(self, obs, actions, bn="sample"):
-        """network.py:117-152: (log_probs, entropies) of given actions."""
-        mean, std = self.heads(obs, bn)
-        dist = Normal(mean, std)
-        return dist.log_prob(actions), dist.entropy()
-
-
-class BatchedCritic(nn.Module):
-    """network.py:154-172 `Value` (already batched in the reference): the
-    centralised critic over the concatenated observations of one side."""
-
-    def __init__(self, n_inputs):
-        super().__init__()
-        self.fc1 = nn.Linear(n_inputs, 32, bias=True)
-        self.fc2 = nn.Linear(32, 64, bias=True)
-        self.fc3 = nn.Linear(64, 64, bias=True)
-        self.fc4 = nn.Linear(64, 1)
-        for m in (self.fc1, self.fc2, self.fc3, self.fc4):
-            nn.init.xavier_uniform_(m.weight)
-
-    def load_reference(self, state_dict):
-        self.load_state_dict({k: torch.as_tensor(np.asarray(v)) for k, v in state_dict.items()})
-        return self
-
-    def packed(self, n_ships, obs_dim):
-        """Parameters in lnw_rollout_post's order (csrc/lnw_actor.hip): the MFMA
-        A-operand fragments of fc1 per ship (its obs_dim inputs zero-padded to
-        a multiple of 16), b1; fc2 fragments, b2; fc3 fragments, b3; fc4 w
-        [64], b (+ 3 zeros). Fragments: float4 [n-tile][k-quad][lane] =
-        W[16 nt + lane % 16][16 q + 4 (lane // 16) + 0..3] (BatchedActor.packed_policy)."""
-        dev = self.fc1.weight.device
-
-        def frags(w, k_pad, n_pad):
-            wp = torch.zeros((n_pad, k_pad), dtype=torch.float32, device=dev)
-            wp[:w.shape[0], :w.shape[1]] = w.detach().float()
-            return wp.reshape(n_pad // 16, 16, k_pad // 16, 4, 4).permute(0, 2, 3, 1, 4).reshape(-1)
-
-        dq = (obs_dim + 15) // 16
-        w1 = self.fc1.weight.detach().float().reshape(32, n_ships, obs_dim)
-        f1 = torch.cat([frags(w1[:, i], 16 * dq, 32) for i in range(n_ships)])
-        parts = [f1, self.fc1.bias, frags(self.fc2.weight, 32, 64), self.fc2.bias,
-                 frags(self.fc3.weight, 64, 64), self.fc3.bias, self.fc4.weight.reshape(-1),
-                 self.fc4.bias, torch.zeros(3, device=dev)]
-        return torch.cat([p.detach().reshape(-1).float() for p in parts]).contiguous()
-
-    def forward(self, x):
-        x = torch.flatten(x, 1)
-        x = torch.tanh(self.fc1(x))
-        x = torch.tanh(self.fc2(x))
-        x = torch.tanh(self.fc3(x))
-        return self.fc4(x)
-
-
-# ---- parameter noise (ppo.py:452-482): flat and packed actor vectors -----------
-# The flat layout is the learner's (layout.actor_slices, include/lnw.h), the
-# packed one what lnw_policy_act reads (BatchedActor.packed_policy()).
-NOISE_FREE = ("norm1", "norm2", "layernorm")  # name parts the reference leaves alone (ppo.py:470-473)
-
-
-def flat_n_in(P):
-    """n_in of a flat actor vector of P floats (P = 7139 + 66 n_in)."""
-    n_in, rem = divmod(int(P) - 7139, 66)
-    if rem or n_in < 12:
-        raise ValueError(f"{P} floats is no flat actor vector")
-    return n_in
-
-
-def noise_mask(n_in, device=None):
-    """float32 [P], 1 where parameter noise is added, in the flat layout: every
-    weight and bias of conv1, conv2, convhead, fc1, fc2, fc3 and the two heads; 0
-    on norm1.*, norm2.* (running statistics included), layernorm.* and the logstd
-    slot (which the reference noises, and nothing reads)."""
-    sl = actor_slices(n_in)
-    m = torch.zeros(flat_size(sl), dtype=torch.float32)
-    for name, (k, shp) in sl.items():
-        if name != "logstd" and not any(s in name for s in NOISE_FREE):
-            m[k:k + int(np.prod(shp))] = 1.0
-    return m.to(device) if device is not None else m
-
-
-def unpack_policy(packed, n_in):
-    """The inverse of BatchedActor.packed_policy(): packed sets [..., floats] to
-    flat vectors [..., P], bit for bit (hi + mid + lo of a weight's three
-    bfloat16 terms is exact in float32). The logstd slot, which the packed set
-    does not hold, is 0."""
-    sl = actor_slices(n_in)
-    P = flat_size(sl)
-    x = packed.reshape(-1, packed.shape[-1])
-    M = x.shape[0]
-    out = torch.zeros((M, P), dtype=torch.float32, device=x.device)
-    n_par = CONV_PARAMS + 2 * n_in
-    out[:, :n_par] = x[:, :n_par]
-    o = (n_par + 3) & ~3
-    for name, cnt in (("fc1.bias", 64), ("fc2.bias", 64), ("fc3.bias", 32)):
-        out[:, sl[name][0]:sl[name][0] + cnt] = x[:, o:o + cnt]
-        o += cnt
-    for name, k_pad, n_pad, rows, cols in (("fc1.weight", 32 if n_in <= 32 else 64, 64, 64, n_in),
-                                           ("fc2.weight", 64, 64, 64, 64), ("fc3.weight", 64, 32, 32, 64),
-                                           ("normal_head.weight", 32, 16, 8, 32)):  # (+ log_std_head, adjacent)
-        nt, qp = n_pad // 16, k_pad // 32
-        cnt = 3 * nt * qp * 64 * 4
-        pl = x[:, o:o + cnt].contiguous().view(torch.bfloat16).reshape(M, 3, nt, qp, 64, 8).float()
-        o += cnt
-        w = (pl[:, 0] + pl[:, 1]) + pl[:, 2]
-        # [nt][p][lane = 16 g + m][j = 4 half + v] -> [nt][m][p][half][g][v]
-        w = w.reshape(M, nt, qp, 4, 16, 2, 4).permute(0, 1, 4, 2, 5, 3, 6).reshape(M, n_pad, k_pad)
-        out[:, sl[name][0]:sl[name][0] + rows * cols] = w[:, :rows, :cols].reshape(M, -1)
-    return out.reshape(packed.shape[:-1] + (P,))
 
 
 def perturbed_theta(theta, member0, members, std, clip, seed, call, T, dtype=torch.float32):

@@ -56,7 +56,8 @@ def test_import_graph_has_no_cycle():
     graph = {os.path.basename(p)[:-3]: lnw_imports(p) for p in glob.glob(os.path.join(LNW, "*.py"))}
     assert graph["layout"] == set()
     assert graph["keyed"] <= {"_abi", "layout"}
-    ring = ("layout", "keyed", "rollout", "ppolearn", "qlearn", "ppodist", "replay")
+    assert graph["nets"] == {"_abi", "layout", "keyed"}
+    ring = ("layout", "keyed", "nets", "rollout", "ppolearn", "qlearn", "ppodist", "replay")
     assert set(ring) <= set(graph)
     done, path = set(), []
 
